@@ -18,11 +18,20 @@ Metric (BASELINE.json): LML evals/sec + train+predict wall-clock, Goku multi-bin
               it: it stays ~flat in N for the same reason.
   inputs    = rank 0 reads the reference's Goku txt files (tests/golden/data) and
               RCCL-broadcasts them once; no collective inside the timed loop.
+  plain run = set-up, warm-up, the timed steps, the outputs (--dump-outputs DIR) and the result
+              line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...); nothing else.
+  --full    = the plain run plus every extra below, measured after the headline timing.
   extras    = train_predict_s: the notebook protocol optimize(1000, lr=0.1) +
               predict_f(X_test) wall-clock of a fresh model, after one untimed predict_f
               (per-process kernel loading) (max over ranks); roofline of the
               dominant kernel family from live hipEvent phase times; cpu_baseline:
-              the fp64 oracle (oracle/mfgp_oracle.py) timed on this host (rank 0, N=1).
+              the fp64 oracle (oracle/mfgp_oracle.py) timed on this host (rank 0, N=1); the hbs /
+              goku_svgp / synth sub-objects (the other BASELINE configs); at N > 1 the
+              shared-theta line of the same job.
+  outputs   = --dump-outputs DIR writes what the timed path left after its last step, as a caller
+              of optimize() receives it (loss history, constrained and unconstrained parameters),
+              as DIR/<name>.npy in float64.  The inputs are the committed data files and fixed
+              initial parameters, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -103,6 +112,23 @@ def load_goku():
     ps = PowerSpecs()
     ps.read_from_txt(GOKU)
     return multifidelity_training_set(ps)
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6   # of file bytes, all outputs together
+
+
+def dump_outputs(outdir, arrays, rank=0, world=1):
+    """--dump-outputs: every array as outdir/<name>.npy (float64; <name>_rank<r> at N > 1), at most
+    DUMP_MAX_BYTES in all: an array over its equal share of that is cut to a fixed sample of its
+    entries (sorted indices drawn with seed 0, the same in every run)."""
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(len(arrays), 1) - 256   # 256: room for the .npy header
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+        if a.nbytes > share:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, share // 8, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
 
 
 def bcast_label(world):
@@ -346,21 +372,23 @@ def svgp_step_mfma_flops(n, m, L, nb=32):
     return L * (fwd + rev) * 2 * nb ** 3
 
 
-def svgp_leg(X, Yr, Xt, steps, warmup, world=1, device=None, train_predict=True, latent=True):
+def svgp_leg(X, Yr, Xt, steps, warmup, world=1, device=None, train_predict=True, latent=True, outputs=None):
     """BASELINE configs[3]: the Goku SVGP models of notebooks/demo: goku power spectra.ipynb --
     SingleBinSVGP (M=300 KMeans centres, L=P=64; cell 10, 1000 iterations, published 2237.47 s on
     the M1) and LatentMFCoregionalizationSVGP (L=15, M=300; published 1020.22 s for 2000).  A step
     is one optimize() iteration: ELBO + analytic gradient + Keras Adam with the CosineDecay
     schedule, replayed from hipGraphs (graphs captured in warm-up).  N > 1: each rank trains the
     single-bin model of its own bin block (per-shard Z / noise, no collective).  Returns the
-    per-rank times and the line's fields."""
+    per-rank times and the line's fields.  outputs: a dict that receives each timed trainer's loss
+    history and packed constrained parameters (Z | theta | q_mu | q_sqrt | W | noise) after its
+    last step (--dump-outputs)."""
     import multi_fidelity_gpflow_amd as M
     n, d = X.shape[0], X.shape[1] - 1
     pr = Yr.shape[1]
     K, W = steps, warmup
     kern = lambda: M.SquaredExponential(lengthscales=np.ones(d))
 
-    def timed(model, max_iters):
+    def timed(model, max_iters, tag):
         tr = M.svgp._SVGPTrainer(model, (X, Yr), max_iters=max_iters, initial_lr=0.1, graph=True, graph_chunk=10)
         tr.run(W)
         with torch.cuda.stream(tr.stream):
@@ -378,16 +406,19 @@ def svgp_leg(X, Yr, Xt, steps, warmup, world=1, device=None, train_predict=True,
             t = torch.tensor([dt], dtype=torch.float64, device=device)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
+        if outputs is not None:
+            outputs[tag + "_loss_history"] = tr.loss_hist[:tr.done].cpu().numpy()
+            outputs[tag + "_params"] = tr.c.cpu().numpy()
         tr.close()
         return dt
 
     sb = M.SingleBinSVGP(X, Yr, kern(), kern(), pr, Z=np.zeros((300, d + 1)))
-    dt_sb = timed(sb, K + W)
+    dt_sb = timed(sb, K + W, "singlebin")
     dt_lat = None
     if latent:
         lat = M.LatentMFCoregionalizationSVGP(X, Yr, kern(), kern(), num_latents=min(15, pr), num_inducing=300,
                                               num_outputs=pr, w_type="diagonal", window_fraction=0.4, scale=0.2)
-        dt_lat = timed(lat, max(K + W, 2000))
+        dt_lat = timed(lat, max(K + W, 2000), "latent")
     # notebook protocol for the single-bin model: a fresh model, optimize(max_iters=1000, initial_lr=0.1)
     train_s = None
     if train_predict:
@@ -443,10 +474,13 @@ def bench_svgp(args):
     from multi_fidelity_gpflow_amd.distributed import bin_block
     b0, b1 = bin_block(Y.shape[1], rank, world)
     Yr = np.ascontiguousarray(Y[:, b0:b1])
+    outputs = {} if args.dump_outputs else None
     leg = svgp_leg(X, Yr, Xt, args.steps, args.warmup, world, device, train_predict=not args.no_train_predict,
-                   latent=not args.no_latent)
+                   latent=not args.no_latent, outputs=outputs)
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs, rank, world)
     shared = shared_inducing_leg(X, Yr, min(args.steps, 50), min(args.warmup, 5), rank, world, device) \
-        if world > 1 else None
+        if world > 1 and args.full else None
     if rank == 0:
         cfg = dict(leg.pop("config"), parallelism=f"bins{world}" if world > 1 else "single")
         line = {
@@ -717,6 +751,13 @@ def main():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--tile", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline timing also measure everything else the line can carry: train+predict "
+                         "wall-clock, roofline, CPU baseline, the hbs / goku_svgp / synth sub-objects, the latent "
+                         "SVGP model, the shared-theta / shared-inducing lines at N > 1 (the --no-* options below "
+                         "drop single items of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path left after its last step as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train-predict", action="store_true")
     ap.add_argument("--no-latent", action="store_true",
@@ -739,6 +780,9 @@ def main():
         sys.exit(spawn_ranks(args.gpus))
     if world_env is not None and int(world_env) != args.gpus:
         sys.exit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world_env}")
+    if not args.full:
+        # a plain run measures the headline figure only
+        args.no_cpu_baseline = args.no_train_predict = args.no_extras = args.no_latent = True
     if args.config == "synth":
         args.no_cpu_baseline = True
         args.no_train_predict = True
@@ -805,6 +849,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     sess.finish()
+    if args.dump_outputs:
+        tm = model._theta_map()
+        dump_outputs(args.dump_outputs, {"loss_history": model.loss_history, "theta": tm.theta(), "u": tm.u()},
+                     rank, world)
 
     # train + predict wall-clock (notebook protocol, fresh model).  The process's first predict_f
     # loads the predict kernels' code and sizes their workspace (~60 ms once per process,
@@ -831,10 +879,12 @@ def main():
     # with the reference's trajectory (SharedThetaTrainer: every rank its bin block, one all-reduce
     # of 1 + G doubles per step), so a scaling run records both
     shared_sub = None
-    if world > 1 and args.mode == "shard" and not synth:
+    if world > 1 and args.mode == "shard" and not synth and args.full:
         shared_sub = shared_theta_leg(X, Yr, min(K, 100), min(W, 10), device)
 
-    roof = roofline_f32(model) if synth else roofline(model, n, Yr.shape[1], d)
+    roof = None
+    if args.full:
+        roof = roofline_f32(model) if synth else roofline(model, n, Yr.shape[1], d)
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(X, Y)

@@ -34,7 +34,10 @@ def _run(backend, tmp_path):
     env.setdefault("NCCL_SOCKET_IFNAME", "lo")
     r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "tests", "_dist_ws1_worker.py"), backend,
                         str(_free_port()), out], env=env, capture_output=True, text=True, timeout=240)
-    assert r.returncode == 0, f"{backend} worker failed ({r.returncode}):\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
+    # the interpreter's fatal-error dump ends in one line naming every loaded extension module,
+    # thousands of characters long: left out, so that the tail shows the error above it
+    err = "\n".join(ln for ln in r.stderr.splitlines() if not ln.startswith("Extension modules:"))
+    assert r.returncode == 0, f"{backend} worker failed ({r.returncode}):\n{r.stdout[-3000:]}\n{err[-3000:]}"
     return dict(np.load(out))
 
 

@@ -22,12 +22,12 @@ for r in $(seq 1 "$R"); do
     k=$((k + 1)); f="$O/${MODE}_${k}_$r"
     case "$MODE" in
       goku)
-        MFGP_LIB_PATH=$(libpath "$it") timeout -k 10 200 python bench.py --no-extras --no-cpu-baseline \
+        MFGP_LIB_PATH=$(libpath "$it") timeout -k 10 200 python bench.py --full --no-extras --no-cpu-baseline \
           --no-train-predict > "$f.json" 2> "$f.err" || exit 3
         python -c "import json; d=json.load(open('$f.json')); print('round $r [$it]', d['value'], 'evals/s', d['ms_per_step'], 'ms', d['roofline']['phase_ms'])" ;;
       env)
         envs=""; [ "$it" != "-" ] && envs="$it"
-        env $envs timeout -k 10 300 python bench.py --no-extras --no-cpu-baseline --no-train-predict \
+        env $envs timeout -k 10 300 python bench.py --full --no-extras --no-cpu-baseline --no-train-predict \
           > "$f.json" 2> "$f.err" || exit 3
         python -c "import json; d=json.load(open('$f.json')); print('round $r [$it]', d['value'], 'evals/s', d['ms_per_step'], 'ms', d['roofline']['phase_ms'])" ;;
       svgp)
@@ -35,7 +35,7 @@ for r in $(seq 1 "$R"); do
           > "$f.json" 2> "$f.err" || exit 3
         python -c "import json; d=json.loads(open('$f.json').read().splitlines()[-1]); print('round $r [$it]', round(d['s_per_iter']*1e3, 4), 'ms')" ;;
       synth)
-        MFGP_LIB_PATH=$(libpath "$it") timeout -k 10 200 python bench.py --config synth --steps 6 --warmup 2 \
+        MFGP_LIB_PATH=$(libpath "$it") timeout -k 10 200 python bench.py --full --config synth --steps 6 --warmup 2 \
           --no-cpu-baseline > "$f.json" 2> "$f.err" || exit 3
         python -c "import json; d=json.load(open('$f.json')); r=d['roofline']; print('round $r [$it]', d['ms_per_step'], round(r['frac'], 4), r['phase_ms'])" ;;
       *) echo "unknown mode $MODE"; exit 2 ;;

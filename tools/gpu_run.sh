@@ -5,7 +5,7 @@
 #   tests            the whole -m gpu suite                       -> OUTDIR/gpu_tests.log
 #   pytest:ARGS      pytest on ARGS (comma-separated words)      -> OUTDIR/pytest_N.log
 #   smoke            __graft_entry__.smoke()                      -> OUTDIR/smoke.log
-#   bench[:ARGS]     bench.py ARGS (comma-separated)              -> OUTDIR/bench_N.json
+#   bench[:ARGS]     bench.py ARGS (comma-separated; --full for every sub-object) -> OUTDIR/bench_N.json
 #   dist2:CFG        two gloo ranks sharing the GPU, bench.py --gpus 2 --config CFG
 #   profile:CFG      tools/profile_round.sh (trace + PMC passes)  -> OUTDIR/CFG/
 #   py:SCRIPT[,ARGS] python SCRIPT ARGS                           -> OUTDIR/py_N.log
@@ -40,7 +40,7 @@ for step in "$@"; do
       head -c 600 "$O/bench_$i.json"; echo ;;
     dist2)
       MFGP_DIST_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-        --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 2 --config "$arg" --no-cpu-baseline \
+        --master-addr 127.0.0.1 --master-port 29541 bench.py --full --gpus 2 --config "$arg" --no-cpu-baseline \
         > "$O/dist2_$arg.out" 2> "$O/dist2_$arg.err"; rc=$?
       grep '^{' "$O/dist2_$arg.out" > "$O/dist2_$arg.json" ;;
     profile)
