@@ -124,7 +124,7 @@ def info_error(v: int, what: str):
     if v == MFGP_FLOW_TIMEOUT:
         return FlowTimeoutError(f"{what}: the persistent Cholesky timed out waiting for a hand-off "
                                 f"(info {v}); set MFGP_FLOW=0 / Engine.set_flow(False) to use the step schedule")
-    from .models import CholeskyError
+    from .session import CholeskyError
     return CholeskyError(f"{what}: Cholesky decomposition was not successful "
                          f"(non-positive pivot at row {v}); the input might not be valid.")
 

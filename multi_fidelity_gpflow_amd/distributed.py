@@ -17,6 +17,10 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .params import Parameter
+from .session import _PackedAdam, _Session, check_outcome, span_from_tie
+from .svgp import _SVGPTrainer
+
 
 def bin_block(p: int, rank: int, world: int):
     """Contiguous [b0, b1) block of the p bins owned by `rank`."""
@@ -92,7 +96,12 @@ def _graph_default() -> bool:
     return dist.get_backend() == "nccl"
 
 
-class SharedThetaTrainer:
+def _allreduce_sum(t):
+    if dist.is_available() and dist.is_initialized():
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+
+
+class SharedThetaTrainer(_Session):
     """Reference-parity multi-GPU training of ONE multi-bin model (SURVEY §8(e) shared-theta
     mode).  Every rank holds the full X and its contiguous bin block of Y; per Adam
     iteration it evaluates the block's LML and dLML/dtheta (the shared Gram / Cholesky is
@@ -108,88 +117,59 @@ class SharedThetaTrainer:
     all-reduce captured inside them (`graph`: None = that default; gloo runs eagerly).  The three
     hooks can be replaced (CPU rehearsal with gloo)."""
 
+    fence = True
+
     def __init__(self, model, lr, max_iters, lml_grad=None, allreduce=None, adam=None, graph=None,
                  graph_chunk=50):
-        from .engine import Engine
         self.model = model
-        self.max_iters = max(int(max_iters), 1)
-        tm = model._theta_map()
-        self.tm = tm
-        G = len(tm.entries)
-        u = tm.u()
-        trainable = tm.trainable().astype(np.uint8)
-        transform = np.ones(G, np.uint8)
-        transform[tm.noise_index] = 2
-        tie = tm.tie()
-        span = np.ones(G, np.uint8)
-        for q in range(G):
-            lead = int(np.argmax(tie == tie[q]))
-            if lead != q:
-                span[q] = 0
-                span[lead] += 1
-        self.done = 0
-        self.hist = []
-        self.stream = None
-        self.allreduce = allreduce or (lambda t: dist.all_reduce(t, op=dist.ReduceOp.SUM)
-                                       if dist.is_available() and dist.is_initialized() else None)
-        if lml_grad is None:   # MI355X path
-            eng, X, Y = model._device_data()
-            dev = eng.device
-            f64 = dict(dtype=torch.float64, device=dev)
-            self.eng = eng
-            self.stream = torch.cuda.Stream(dev)
-            self.stream.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(self.stream):
-                # every buffer a captured step points at is the trainer's own (ADVICE r5: the
-                # workspace too -- the engine's shared one may be written by other calls between
-                # steps, and a resident step would then skip a set-up it needs)
-                self.X, self.Y = X.clone(), Y.clone()
-                n, p, d = X.shape[0], Y.shape[1], X.shape[1] - 1
-                self.ws = eng.private_workspace(eng.gpr_workspace_bytes(n, p, d))
-                self.theta = torch.tensor(tm.theta(), **f64)
-                self.u = torch.tensor(u, **f64)
-                self.m = torch.zeros(G, **f64)
-                self.v = torch.zeros(G, **f64)
-                self.trainable = torch.tensor(trainable, device=dev)
-                self.transform = torch.tensor(transform, device=dev)
-                self.span = torch.tensor(span, device=dev)
-                self.step_t = torch.zeros((1,), dtype=torch.int32, device=dev)
-                self.lr = torch.full((self.max_iters,), float(np.float32(lr)), **f64)
-                self.hist_t = torch.zeros((self.max_iters,), **f64)
-                self.out = torch.zeros((1 + G,), **f64)
-                self.info = torch.zeros((1,), dtype=torch.int32, device=dev)
-                self.bad = torch.zeros((1,), dtype=torch.int32, device=dev)
-            self.b1, self.b2 = float(np.float32(0.9)), float(np.float32(0.999))
-
-            def _lml_grad():
-                # every step is a value+grad call of the same problem on the private workspace,
-                # which leaves it set up for the next (mfgp_set_resident)
-                with eng.resident():
-                    eng.gpr_lml(self.X, self.Y, self.theta, want_grad=True, ws=self.ws, out=self.out, info=self.info)
-                return self.out
-
-            def _adam(out):
-                # the reduced LML is NaN on every rank when any rank's evaluation failed (its
-                # finalize writes NaN): all ranks then skip the update and keep the step counter
-                torch.ne(out[:1], out[:1], out=self._isnan)   # NaN test, no allocation
-                self.bad.copy_(self._isnan)
-                eng.adam_packed(self.u, self.theta, out[1:], self.m, self.v, self.trainable, self.transform,
-                                self.span, self.step_t, self.lr, self.b1, self.b2, 1e-7, out, 1.0, self.hist_t,
-                                None, info=self.bad)
-            self._isnan = torch.zeros((1,), dtype=torch.bool, device=dev)
-            self.lml_grad, self.adam = _lml_grad, _adam
-            if graph is None:
-                graph = _graph_default()
-            self.graph_chunk = int(graph_chunk) if graph else 0
-            self._warm = False
-        else:
+        self.tm = tm = model._theta_map()
+        self.allreduce = allreduce or _allreduce_sum
+        self.opt = None
+        if lml_grad is not None:   # CPU rehearsal: no stream, no device state, eager steps
             self.lml_grad, self.adam = lml_grad, adam
             self.graph_chunk = 0
-            self._warm = True
-        from .models import _StepRunner
-        self.runner = _StepRunner(self._one, self.graph_chunk)
+            super().__init__(None, max_iters, 0)
+            return
+        eng, X, Y = model._device_data()   # MI355X path
+        if graph is None:
+            graph = _graph_default()
+        self.graph_chunk = int(graph_chunk) if graph else 0
+        super().__init__(eng, max_iters, self.graph_chunk, warm=False)
+        dev = eng.device
+        G = len(tm.entries)
+        transform = np.ones(G, np.uint8)
+        transform[tm.noise_index] = 2
+        with self._ctx(fence=False):
+            # every buffer a captured step points at is the trainer's own (ADVICE r5: the
+            # workspace too -- the engine's shared one may be written by other calls between
+            # steps, and a resident step would then skip a set-up it needs)
+            self.X, self.Y = X.clone(), Y.clone()
+            n, p, d = X.shape[0], Y.shape[1], X.shape[1] - 1
+            self.ws = eng.private_workspace(eng.gpr_workspace_bytes(n, p, d))
+            self.opt = _PackedAdam(dev, tm.u(), tm.theta(), tm.trainable(), transform, span_from_tie(tm.tie()),
+                                   np.full(self.max_iters, float(np.float32(lr))))
+            self.theta = self.opt.c
+            self.out = torch.zeros((1 + G,), dtype=torch.float64, device=dev)
+            self.info = torch.zeros((1,), dtype=torch.int32, device=dev)
+            self.bad = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self._isnan = torch.zeros((1,), dtype=torch.bool, device=dev)
 
-    def _one(self):
+        def _lml_grad():
+            # every step is a value+grad call of the same problem on the private workspace,
+            # which leaves it set up for the next (mfgp_set_resident)
+            with eng.resident():
+                eng.gpr_lml(self.X, self.Y, self.theta, want_grad=True, ws=self.ws, out=self.out, info=self.info)
+            return self.out
+
+        def _adam(out):
+            # the reduced LML is NaN on every rank when any rank's evaluation failed (its
+            # finalize writes NaN): all ranks then skip the update and keep the step counter
+            torch.ne(out[:1], out[:1], out=self._isnan)   # NaN test, no allocation
+            self.bad.copy_(self._isnan)
+            self.opt.apply(eng, out[1:], out, 1.0, self.bad)
+        self.lml_grad, self.adam = _lml_grad, _adam
+
+    def _step(self):
         out = self.lml_grad()
         self.allreduce(out)
         self.adam(out)
@@ -197,67 +177,20 @@ class SharedThetaTrainer:
     def step(self):
         self.run(1)
 
-    def _ctx(self):
-        import contextlib
-        if self.stream is None:
-            return contextlib.nullcontext()
-        st = contextlib.ExitStack()
-        st.enter_context(torch.cuda.stream(self.stream))
-        st.enter_context(self.eng.ordered(self.stream))
-        return st
-
-    def run(self, n):
-        if self.done + n > self.max_iters:
-            raise ValueError("SharedThetaTrainer: more iterations than max_iters")
-        if n <= 0:
-            return
-        with self._ctx():
-            if not self._warm:
-                # the first step runs eagerly: the communicator, the workspace set-up and the
-                # kernels' launch attributes exist before any capture
-                self._one()
-                self.done += 1
-                n -= 1
-                self._warm = True
-            self.runner.run(n)
-        self.done += n
-
-    def prepare(self, n):
-        """Capture the graphs a later run(n) replays (nothing executes; after the first step)."""
-        if self.stream is not None and self._warm:
-            with torch.cuda.stream(self.stream):
-                self.runner.prepare(n)
-
-    def sync(self):
-        if self.stream is not None:
-            self.stream.synchronize()
-
-    def close(self):
-        self.runner.close()
-
     def finish(self):
         """Write theta back into the model (device path) and its loss_history."""
-        from ._lib import MFGP_FLOW_TIMEOUT, MFGPError, info_error
-        from .models import CholeskyError
-        if not hasattr(self, "u"):
+        if self.opt is None:
             return
         self.sync()
         self.close()
-        self.tm.set_u(self.u.cpu().numpy())
-        h = self.hist_t[:self.done].cpu().numpy()
+        self.tm.set_u(self.opt.u.cpu().numpy())
+        h = self.opt.hist[:self.done].cpu().numpy()
         self.model.loss_history = [np.float64(v) for v in h]
-        v = int(self.info.item())
-        steps = int(self.step_t.item())
-        if v == MFGP_FLOW_TIMEOUT:
-            raise info_error(v, "shared-theta optimize")
-        if v == 0 and steps != self.done and np.all(np.isfinite(h)):
-            raise MFGPError(f"shared-theta optimize: {self.done - steps} of {self.done} steps failed on some rank "
-                            f"and were retried; the trajectory is incomplete")
-        if v != 0 or not np.all(np.isfinite(h)):
-            raise CholeskyError("shared-theta optimize: Cholesky failed")
+        check_outcome("shared-theta optimize", self.info.item(), int(self.opt.step.item()), self.done, h,
+                      cause=" on some rank")
 
 
-class SharedInducingTrainer:
+class SharedInducingTrainer(_Session):
     """SURVEY §8(e) sharding of ONE SingleBinSVGP (singlebin_svgp.py:39-62): every per-bin quantity
     (kernel theta_l, q_mu[:, l], q_sqrt[l]) lives on the rank that owns bin l, while the inducing
     inputs Z and the Gaussian noise are shared, trainable parameters of the one model.  The
@@ -279,8 +212,8 @@ class SharedInducingTrainer:
     def __init__(self, model=None, data=None, max_iters=1, initial_lr=0.1, grad=None, shared=None, adam=None,
                  allreduce=None, graph=None, graph_chunk=50):
         self.tr = None
+        self.graph_chunk = 0
         if grad is None:   # MI355X path
-            from .svgp import _SVGPTrainer
             tr = _SVGPTrainer(model, data, max_iters, initial_lr, graph=False)
             self.tr = tr
             self.gate = torch.zeros((1,), dtype=torch.int32, device=tr.eng.device)
@@ -297,31 +230,21 @@ class SharedInducingTrainer:
 
             def _adam(failed):
                 self.gate.copy_(failed.reshape(1) > 0)
-                tr.eng.adam_packed(tr.u, tr.c, tr.g, tr.mo, tr.vo, tr.trainable, tr.transform, tr.span, tr.step_t,
-                                   tr.lr, tr.b1, tr.b2, 1e-7, tr.out, tr.klm, tr.loss_hist, tr.kl_hist,
-                                   info=self.gate)
+                tr.opt.apply(tr.eng, tr.g, tr.out, tr.klm, self.gate)
             grad, adam = _grad, _adam
-            self.stream = tr.stream
-        else:
-            self.stream = None
+            if graph is None:
+                graph = _graph_default()
+            self.graph_chunk = int(graph_chunk) if graph else 0
+        # on the inner trainer's stream; with graphs the first step runs eagerly (the communicator
+        # and the workspace exist before any capture)
+        tr = self.tr
+        super().__init__(tr and tr.eng, max_iters, self.graph_chunk, stream=tr and tr.stream,
+                         warm=self.graph_chunk == 0)
         self.grad_fn, self.adam_fn, self.shared = grad, adam, list(shared)
         self.sizes = [t.numel() for t in self.shared]
         t0 = self.shared[0]
         self.buf = torch.zeros(sum(self.sizes) + 1, dtype=torch.float64, device=t0.device)
-        self.allreduce = allreduce or (lambda t: dist.all_reduce(t, op=dist.ReduceOp.SUM)
-                                       if dist.is_available() and dist.is_initialized() else None)
-        self.done = 0
-        self.max_iters = max(int(max_iters), 1)
-        if self.tr is not None and graph is None:
-            graph = _graph_default()
-        self.graph_chunk = int(graph_chunk) if (graph and self.tr is not None) else 0
-        self._warm = self.graph_chunk == 0
-        from .models import _StepRunner
-        self.runner = _StepRunner(self._one, self.graph_chunk)
-
-    def _ctx(self):
-        import contextlib
-        return torch.cuda.stream(self.stream) if self.stream is not None else contextlib.nullcontext()
+        self.allreduce = allreduce or _allreduce_sum
 
     def pack(self):
         """Local evaluation, then its shared part into the reduction buffer."""
@@ -340,7 +263,7 @@ class SharedInducingTrainer:
             o += n
         self.adam_fn(self.buf[o:o + 1])
 
-    def _one(self):
+    def _step(self):
         self.pack()
         self.allreduce(self.buf)
         self.unpack_step()
@@ -348,31 +271,10 @@ class SharedInducingTrainer:
     def step(self):
         self.run(1)
 
-    def run(self, n):
-        if self.done + n > self.max_iters:
-            raise ValueError("SharedInducingTrainer: more iterations than max_iters")
-        if n <= 0:
-            return
-        with self._ctx():
-            if not self._warm:
-                # the first step runs eagerly (communicator and workspace exist before any capture)
-                self._one()
-                self._count(1)
-                n -= 1
-                self._warm = True
-            self.runner.run(n)
-        self._count(n)
-
     def _count(self, n):
-        self.done += n
+        super()._count(n)
         if self.tr is not None:   # the device trainer's own count (its finish() reads that many losses)
             self.tr.done = self.done
-
-    def prepare(self, n):
-        """Capture the graphs a later run(n) replays (nothing executes; after the first step)."""
-        if self._warm and self.graph_chunk:
-            with self._ctx():
-                self.runner.prepare(n)
 
     def set_trainable(self, name, flag):
         self.tr.set_trainable(name, flag)
@@ -390,12 +292,8 @@ class SharedInducingTrainer:
                 self.set_trainable("noise", True)
         self.finish()
 
-    def sync(self):
-        if self.tr is not None:
-            self.tr.sync()
-
     def finish(self):
-        self.runner.close()
+        self.close()
         if self.tr is not None:
             self.tr.finish()
 
@@ -403,7 +301,6 @@ class SharedInducingTrainer:
 def broadcast_inducing(model, rank: int, world: int, device):
     """Make the model's inducing inputs identical on every rank (rank 0's KMeans centres: the
     host KMeans can differ in the last ulp between processes)."""
-    from .params import Parameter
     Z = broadcast_arrays([model.inducing_variable.numpy()] if rank == 0 else None, rank, world, device)[0]
     model.inducing_variable = Parameter(np.ascontiguousarray(Z, dtype=np.float64))
     return model

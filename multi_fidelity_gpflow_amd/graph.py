@@ -18,9 +18,11 @@ import torch
 
 from .engine import Engine, to_dev
 from .kernels import GraphMultiFidelityKernel
-from ._lib import MFGP_FLOW_TIMEOUT, MFGPError, info_error
-from .models import CholeskyError, Gaussian, _StepRunner
-from .params import Module, Sigmoid, Softplus, as_result, set_trainable
+from ._lib import info_error
+from .models import Gaussian
+from .params import (Module, Sigmoid, Softplus, as_result, gather_entries, scatter_entries, set_trainable,
+                     tie_entries)
+from .session import _PackedAdam, _Session, check_outcome, span_from_tie
 
 
 def _code(prm) -> int:
@@ -63,11 +65,7 @@ class GraphMultiFidelityGPModel(Module):
         return self.kernel.theta_entries(d) + [(self.likelihood.variance, None)]
 
     def _theta(self):
-        vals = []
-        for prm, idx in self._entries():
-            v = prm.numpy()
-            vals.append(float(v if idx is None else np.asarray(v)[idx]))
-        return np.array(vals)
+        return gather_entries(self._entries(), True)
 
     @staticmethod
     def _raise_info(info, what):
@@ -180,57 +178,32 @@ class GraphMultiFidelityGPModel(Module):
             unpack(res.x)
 
 
-class _GraphAdamSession:
+class _GraphAdamSession(_Session):
     """Keras Adam (constant lr) on the graph theta vector, device-resident: per iteration
     one mfgp_gmf_gpr_lml(want_grad) + one mfgp_adam_packed (Softplus / Sigmoid transforms,
     tied isotropic lengthscales), replayed from hipGraphs on a dedicated stream."""
 
+    fence = True
+
     def __init__(self, model: GraphMultiFidelityGPModel, lr, max_iters, graph, chunk):
         self.model = model
-        self.eng, self.X, self.Y = model._device_data()
-        dev = self.eng.device
-        ents = model._entries()
-        G = len(ents)
-        c = np.zeros(G); u = np.zeros(G); tr = np.zeros(G, np.uint8); tf = np.zeros(G, np.uint8)
-        span = np.ones(G, np.uint8)
-        first = {}
-        for q, (prm, idx) in enumerate(ents):
-            cv, uv = prm.numpy(), prm.unconstrained_variable
-            c[q] = float(cv if idx is None else np.asarray(cv)[idx])
-            u[q] = float(uv if idx is None else np.asarray(uv)[idx])
-            tr[q] = prm.trainable
-            tf[q] = _code(prm)
-            key = (id(prm), idx)
-            if key in first:
-                span[q] = 0
-                span[first[key]] += 1
-            else:
-                first[key] = q
+        eng, self.X, self.Y = model._device_data()
+        super().__init__(eng, max_iters, chunk if graph else 0)
+        dev = eng.device
         # rho_LF's diagonal is never used by K (graph.py:62): its gradient is 0 and Adam
         # leaves it; rho[:, 1:] is not in theta at all (only column 0 is used).
-        self.ents = ents
-        self.max_iters = max(int(max_iters), 1)
-        self.stream = torch.cuda.Stream(dev)
-        f64 = dict(dtype=torch.float64, device=dev)
-        with torch.cuda.stream(self.stream), self.eng.ordered(self.stream):
-            self.theta = torch.tensor(c, **f64)
-            self.u = torch.tensor(u, **f64)
-            self.mo = torch.zeros(G, **f64)
-            self.vo = torch.zeros(G, **f64)
-            self.trainable = torch.tensor(tr, device=dev)
-            self.transform = torch.tensor(tf, device=dev)
-            self.span = torch.tensor(span, device=dev)
-            self.step = torch.zeros((1,), dtype=torch.int32, device=dev)
-            self.lr = torch.full((self.max_iters,), float(np.float32(lr)), **f64)
-            self.hist = torch.zeros((self.max_iters,), **f64)
-            self.out = torch.zeros((1 + G,), **f64)
+        self.ents = ents = model._entries()
+        G = len(ents)
+        with self._ctx():
+            self.opt = _PackedAdam(dev, gather_entries(ents, False), gather_entries(ents, True),
+                                   [prm.trainable for prm, _ in ents], [_code(prm) for prm, _ in ents],
+                                   span_from_tie(tie_entries(ents)), np.full(self.max_iters, float(np.float32(lr))))
+            self.theta = self.opt.c
+            self.out = torch.zeros((1 + G,), dtype=torch.float64, device=dev)
             self.info = torch.zeros((1,), dtype=torch.int32, device=dev)
             n, p, d = self.X.shape[0], self.Y.shape[1], self.X.shape[1] - 1
-            self.ws = self.eng.private_workspace(self.eng.gmf_workspace_bytes(self.model.num_LF, n, p, d))
+            self.ws = eng.private_workspace(eng.gmf_workspace_bytes(self.model.num_LF, n, p, d))
             self._lml()   # builds the schedule tables outside capture
-        self.b1, self.b2 = float(np.float32(0.9)), float(np.float32(0.999))
-        self.done = 0
-        self.runner = _StepRunner(self._step, chunk if graph else 0)
 
     def _lml(self):
         self.eng.gmf_lml(self.model.num_LF, self.X, self.Y, self.theta, want_grad=True, out=self.out, info=self.info,
@@ -238,40 +211,12 @@ class _GraphAdamSession:
 
     def _step(self):
         self._lml()
-        self.eng.adam_packed(self.u, self.theta, self.out[1:], self.mo, self.vo, self.trainable, self.transform,
-                             self.span, self.step, self.lr, self.b1, self.b2, 1e-7, self.out, 1.0, self.hist, None,
-                             info=self.info)
-
-    def run(self, n):
-        if self.done + n > self.max_iters:
-            raise ValueError("optimize: more iterations than max_iters")
-        with torch.cuda.stream(self.stream), self.eng.ordered(self.stream):
-            self.runner.run(n)
-        self.done += n
-
-    def close(self):
-        """Release the recorded step graphs now (a later run re-captures)."""
-        self.runner.close()
+        self.opt.apply(self.eng, self.out[1:], self.out, 1.0, self.info)
 
     def finish(self):
-        self.stream.synchronize()
+        self.sync()
         self.close()
-        u = self.u.cpu().numpy()
-        for (prm, idx), uq in zip(self.ents, u):
-            if idx is None:
-                prm.unconstrained_variable = np.full(prm.shape, uq)
-            else:
-                arr = np.array(prm.unconstrained_variable, copy=True)
-                arr[idx] = uq
-                prm.unconstrained_variable = arr
-        h = self.hist[:self.done].cpu().numpy()
+        scatter_entries(self.ents, self.opt.u.cpu().numpy())
+        h = self.opt.hist[:self.done].cpu().numpy()
         self.model.loss_history = [np.float64(v) for v in h]
-        v = int(self.info.item())
-        steps = int(self.step.item())
-        if v == MFGP_FLOW_TIMEOUT:
-            raise info_error(v, "optimize")
-        if v == 0 and steps != self.done and np.all(np.isfinite(h)):
-            raise MFGPError(f"optimize: {self.done - steps} of {self.done} steps failed and were retried; "
-                            f"the trajectory is incomplete")
-        if v != 0 or not np.all(np.isfinite(h)):
-            raise CholeskyError("optimize: Cholesky failed")
+        check_outcome("optimize", self.info.item(), int(self.opt.step.item()), self.done, h)

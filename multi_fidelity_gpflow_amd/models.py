@@ -21,20 +21,18 @@ from __future__ import annotations
 
 import atexit
 import threading
-import weakref
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
-from ._lib import MFGP_FLOW_TIMEOUT, MFGPError, info_error
+from ._lib import MFGPError, info_error
 from .engine import AdamState, Engine, resolve_dtype, theta_size, to_dev
 from .kernels import LinearMultiFidelityKernel
-from .params import Module, Parameter, as_result, positive, set_trainable
-
-
-class CholeskyError(MFGPError):
-    """Analogue of TF's InvalidArgumentError('Cholesky decomposition was not successful')."""
+from .params import (Module, Parameter, as_result, gather_entries, positive, scatter_entries, set_trainable,
+                     tie_entries)
+from .session import (CholeskyError, _Session, _StepRunner, _retire_graphs, _retired_graphs,  # noqa: F401
+                      check_outcome, new_stream, release_retired_graphs)
 
 
 class Gaussian(Module):
@@ -66,44 +64,20 @@ class _ThetaMap:
         assert len(self.entries) == theta_size(d)
         self.noise_index = theta_size(d) - 1
 
-    def _gather(self, which: str) -> np.ndarray:
-        # each Parameter's (constrained or unconstrained) array once, however many entries it owns
-        arrs, out = {}, []
-        for p, idx in self.entries:
-            arr = arrs.get(id(p))
-            if arr is None:
-                arr = arrs[id(p)] = p.numpy() if which == "c" else p.unconstrained_variable
-            out.append(float(arr if idx is None else arr[idx]))
-        return np.array(out)
-
     def theta(self) -> np.ndarray:
-        return self._gather("c")
+        return gather_entries(self.entries, True)
 
     def u(self) -> np.ndarray:
-        return self._gather("u")
+        return gather_entries(self.entries, False)
 
     def trainable(self) -> np.ndarray:
         return np.array([p.trainable for p, _ in self.entries], dtype=bool)
 
     def tie(self) -> np.ndarray:
-        ids, out = {}, []
-        for p, i in self.entries:
-            key = (id(p), i)
-            out.append(ids.setdefault(key, len(ids)))
-        return np.array(out, dtype=np.int32)
+        return tie_entries(self.entries)
 
     def set_u(self, u: np.ndarray):
-        # one assignment per Parameter (entries in order: a later entry of the same index wins)
-        new = {}
-        for (p, idx), val in zip(self.entries, u):
-            if idx is None:
-                new[id(p)] = (p, np.full(p.shape, val))
-            else:
-                arr = new[id(p)][1] if id(p) in new else p.unconstrained_variable.copy()
-                arr[idx] = val
-                new[id(p)] = (p, arr)
-        for p, arr in new.values():
-            p.unconstrained_variable = arr
+        scatter_entries(self.entries, u)
 
 
 class MultiFidelityGPModel(Module):
@@ -368,41 +342,9 @@ def _pool_take(key):
         return _pool.pop(key, None)
 
 
-atexit.register(lambda: release_retired_graphs())
+# registered after session.py's release_retired_graphs, so it runs before it at exit
 atexit.register(clear_session_pool)
 Engine._mode_listeners.append(lambda eng: clear_session_pool())
-
-
-# ---------------------------------------------------------------- retired step graphs
-# The captured step graphs of a closed, released or dropped session are not destroyed before the
-# interpreter exits; they are kept here (no buffers: a graph holds no reference to the tensors it
-# was captured on).  Reason: in the HIP runtime this image ships (libamdhip64 of
-# ROCm 7.0.2, GPU_MAX_HW_QUEUES = 4), instantiating a graph with parallel branches (the fp32
-# lookahead's and the SVGP gradient's fork / join) acquires hardware queues for its internal branch
-# streams, shared by reference count with user streams; destroying such a graph exec after a later
-# user stream came to share one of those queues made the next hipGraphLaunch on it segfault
-# (tools/graph_lifetime_probe.py small_graphs_after: the fifth session's first replay, every run,
-# with AMD_LOG_LEVEL=3 showing the exec's releaseQueue on the queue the new session's stream
-# holds; never with the graphs kept).  A retired graph costs its exec's host nodes and kernel
-# arguments (a few hundred KB at the Synth size); release_retired_graphs() frees them when the
-# caller knows that no captured graph will be launched again in the process.
-_retired_graphs: list = []
-
-
-def _retire_graphs(graphs: dict):
-    if graphs:
-        _retired_graphs.extend(graphs.values())
-        graphs.clear()
-
-
-def release_retired_graphs():
-    """Destroy the retired step graphs now (see above: only when no captured graph is launched in
-    this process afterwards).  Returns how many were destroyed."""
-    n = len(_retired_graphs)
-    if n and torch.cuda.is_available():
-        torch.cuda.synchronize()
-    _retired_graphs.clear()
-    return n
 
 
 class _AdamCore:
@@ -412,8 +354,7 @@ class _AdamCore:
     def __init__(self, eng: Engine, X: torch.Tensor, Y: torch.Tensor, tm: "_ThetaMap", lr: float,
                  max_iters: int):
         self.eng = eng
-        self.stream = torch.cuda.Stream(eng.device)
-        self.stream.wait_stream(torch.cuda.current_stream(eng.device))
+        self.stream = new_stream(eng.device)
         self.graphs = {}
         with torch.cuda.stream(self.stream):
             self.X = torch.empty_like(X)
@@ -483,7 +424,7 @@ def _pool_key(eng, X, Y, lr, max_iters, chunk):
             int(chunk))
 
 
-class AdamSession:
+class AdamSession(_Session):
     """Runs MultiFidelityGPModel Adam iterations on the device.
 
     State (unconstrained u, moments, step counter, loss history) lives in HBM; each
@@ -492,26 +433,28 @@ class AdamSession:
     syncs when asked (progress prints, finish).  finish() hands the buffers and graphs to the
     session pool, so the next session of the same shape replays them without a capture."""
 
+    fence = True
+
     def __init__(self, model: "MultiFidelityGPModel", lr: float, max_iters: int, graph: bool, chunk: int):
         self.model = model
-        self.eng, Xm, Ym = model._device_data()
+        eng, Xm, Ym = model._device_data()
         self.tm = model._theta_map()
-        self.max_iters = max(int(max_iters), 1)
+        max_iters = max(int(max_iters), 1)
         chunk = chunk if graph else 0
-        self._key = _pool_key(self.eng, Xm, Ym, lr, self.max_iters, chunk)
+        self._key = _pool_key(eng, Xm, Ym, lr, max_iters, chunk)
         core = _pool_take(self._key) if chunk else None
         if core is None:
-            core = _AdamCore(self.eng, Xm, Ym, self.tm, lr, self.max_iters)
+            core = _AdamCore(eng, Xm, Ym, self.tm, lr, max_iters)
         self._core = core
-        self.stream, self.st, self.hist, self.out = core.stream, core.st, core.hist, core.out
+        super().__init__(eng, max_iters, chunk, stream=core.stream, graphs=core.graphs)
+        self.st, self.hist, self.out = core.st, core.hist, core.out
         self.info, self.ws, self.X, self.Y = core.info, core.ws, core.X, core.Y
         # every buffer the recorded graphs point at is owned by the core (no shared grow-only
-        # workspace under a graph); loading is ordered on its stream after the caller's work
-        core.stream.wait_stream(torch.cuda.current_stream(self.eng.device))
-        with torch.cuda.stream(self.stream), self.eng.ordered(self.stream):
+        # workspace under a graph); loading is ordered on its stream after the caller's work (a
+        # pooled core's stream is as old as the core)
+        core.stream.wait_stream(torch.cuda.current_stream(eng.device))
+        with self._ctx():
             core.load(Xm, Ym, self.tm)
-        self.done = 0
-        self.runner = _StepRunner(self._step, chunk, graphs=core.graphs)
 
     def _step(self):
         # the session's private workspace is written by its own steps only (and its warm-up, a
@@ -522,37 +465,15 @@ class AdamSession:
     def run(self, n: int):
         if self._core is None:
             raise MFGPError("AdamSession: the session is finished")
-        if self.done + n > self.max_iters:
-            raise ValueError("AdamSession: more iterations than max_iters")
         if self.eng.mode() != self._key[1]:
             # the session's graphs and workspace belong to the settings it started under; a step
             # captured now would run another schedule on them
             raise MFGPError("AdamSession: the engine's tile / flow / tiny settings changed during the session")
-        with torch.cuda.stream(self.stream), self.eng.ordered(self.stream):
-            self.runner.run(n)
-        self.done += n
-
-    def prepare(self, n: int):
-        """Capture the step graphs a later run(n) replays (nothing executes)."""
-        with torch.cuda.stream(self.stream):
-            self.runner.prepare(n)
-
-    def sync(self):
-        self.stream.synchronize()
+        super().run(n)
 
     def loss_at(self, i: int) -> float:
         self.sync()
         return float(self.hist[i].item())
-
-    def close(self):
-        """Release the recorded step graphs now (a later run re-captures)."""
-        self.runner.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def _retire(self):
         """Hand the core (buffers + graphs) to the pool, or release the graphs now.  Either way
@@ -573,11 +494,11 @@ class AdamSession:
         self.close()
 
     def finish(self):
-        n, G, core = self.done, self.st.u.numel(), self._core
+        n, core = self.done, self._core
         if core is None:
             raise MFGPError("AdamSession: the session is finished")
         o = core._off
-        with torch.cuda.stream(self.stream):   # loss history, u, step and info: one byte range, one copy
+        with self._ctx(fence=False):   # loss history, u, step and info: one byte range, one copy
             core.h_out.copy_(core.d_in[:o["tr"]], non_blocking=True)
         self.sync()
         res = core.h_out.numpy()
@@ -587,83 +508,5 @@ class AdamSession:
         si = res[o["si"]:o["tr"]].view(np.int32)
         steps, v = int(si[0]), int(si[1])
         self._retire()
-        if v == 0 and steps != self.done and np.all(np.isfinite(h)):
-            # a failed step leaves the step counter behind and the next one retries it, so a
-            # failure followed by good steps shows only here (trailing loss entries never written)
-            raise MFGPError(f"optimize: {self.done - steps} of {self.done} steps failed (Cholesky or flow "
-                            f"hand-off) and were retried; the trajectory is incomplete")
-        if v != 0 or not np.all(np.isfinite(h)):
-            bad = int(np.argmax(~np.isfinite(h))) if not np.all(np.isfinite(h)) else len(h) - 1
-            self.model.loss_history = self.model.loss_history[:bad + 1]
-            if v == MFGP_FLOW_TIMEOUT:
-                raise info_error(v, f"optimize (by iteration {bad})")
-            raise CholeskyError(f"optimize: Cholesky failed at iteration {bad}")
-
-
-class _StepRunner:
-    """Runs a step function n times: eagerly, or replaying a hipGraph of `chunk`
-    captured steps (torch.cuda.CUDAGraph is the HIP graph API on ROCm).
-
-    Graph lifetime is deterministic: the runner holds its session's step method weakly (no
-    session <-> runner reference cycle), so a session and its hipGraphExecs are freed by
-    reference counting the moment the last reference goes, or at close() -- never by a cyclic
-    collection that could run in the middle of another session's capture (destroying a graph
-    while a stream captures is illegal and aborts the process)."""
-
-    def __init__(self, step, chunk: int, graphs: dict = None):
-        self._step = weakref.WeakMethod(step) if hasattr(step, "__self__") else (lambda f=step: f)
-        self.chunk = chunk
-        self._owns = graphs is None
-        self.graphs = {} if graphs is None else graphs
-
-    def step(self):
-        fn = self._step()
-        if fn is None:
-            raise MFGPError("the training session of this step runner was released")
-        fn()
-
-    def close(self):
-        """Release the captured graphs now (retired until exit, see release_retired_graphs)."""
-        _retire_graphs(self.graphs)
-
-    def __del__(self):
-        # a dropped runner's own graphs are retired too, not destroyed by reference counting (a
-        # session's graphs belong to its _AdamCore, which retires them itself)
-        if getattr(self, "_owns", False):
-            _retire_graphs(self.graphs)
-
-    def _graph(self, n):
-        g = self.graphs.get(n)
-        if g is None:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                for _ in range(n):
-                    self.step()
-            self.graphs[n] = g
-        return g
-
-    def prepare(self, n: int):
-        """Capture (without running) every graph that run(n) will replay, so a later
-        run(n) is replay-only (bench.py captures before its timed region)."""
-        if self.chunk <= 0 or n < 4:
-            return
-        full, rem = divmod(n, self.chunk)
-        if full:
-            self._graph(self.chunk)
-        if rem >= 4:
-            self._graph(rem)
-
-    def run(self, n: int):
-        if self.chunk <= 0 or n < 4:
-            for _ in range(n):
-                self.step()
-            return
-        full, rem = divmod(n, self.chunk)
-        for _ in range(full):
-            self._graph(self.chunk).replay()
-        if rem:
-            if rem < 4:
-                for _ in range(rem):
-                    self.step()
-            else:
-                self._graph(rem).replay()
+        check_outcome("optimize", v, steps, n, h, cause=" (Cholesky or flow hand-off)",
+                      history=self.model.loss_history)

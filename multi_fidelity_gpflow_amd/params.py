@@ -133,6 +133,43 @@ class Parameter:
         return f"Parameter(value={self.numpy()!r}, trainable={self.trainable})"
 
 
+# A theta vector is described by a list of entries (Parameter, index tuple or None): entry q is the
+# scalar Parameter itself (None; one scalar may own several entries, a tied isotropic lengthscale) or
+# one element of an array Parameter.
+
+def gather_entries(entries, constrained: bool) -> np.ndarray:
+    """The entries' constrained or unconstrained values as one flat vector (each Parameter's array
+    is taken once, however many entries it owns)."""
+    arrs, out = {}, []
+    for p, idx in entries:
+        arr = arrs.get(id(p))
+        if arr is None:
+            arr = arrs[id(p)] = p.numpy() if constrained else p.unconstrained_variable
+        out.append(float(arr if idx is None else arr[idx]))
+    return np.array(out)
+
+
+def tie_entries(entries) -> np.ndarray:
+    """Entries that name the same scalar share a number (numbered by first appearance)."""
+    ids = {}
+    return np.array([ids.setdefault((id(p), idx), len(ids)) for p, idx in entries], dtype=np.int32)
+
+
+def scatter_entries(entries, u):
+    """Write a flat unconstrained vector back through the entries: one assignment per Parameter
+    (entries in order: a later entry of the same index wins)."""
+    new = {}
+    for (p, idx), val in zip(entries, u):
+        if idx is None:
+            new[id(p)] = (p, np.full(p.shape, val))
+        else:
+            arr = new[id(p)][1] if id(p) in new else p.unconstrained_variable.copy()
+            arr[idx] = val
+            new[id(p)] = (p, arr)
+    for p, arr in new.values():
+        p.unconstrained_variable = arr
+
+
 class Module:
     """Minimal gpflow.Module: parameters discovered by attribute traversal."""
 

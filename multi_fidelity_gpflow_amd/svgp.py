@@ -22,9 +22,10 @@ import torch
 
 from .engine import Engine, theta_size, to_dev
 from .kernels import LinearCoregionalization, LinearMultiFidelityKernel, SeparateIndependent
-from ._lib import MFGPError
-from .models import CholeskyError, Gaussian, _StepRunner
-from .params import Module, Parameter, Softplus, as_result, parameter_dict, multiple_assign
+from .models import CholeskyError, Gaussian
+from .params import (Module, Parameter, Softplus, as_result, gather_entries, multiple_assign, parameter_dict,
+                     scatter_entries, tie_entries)
+from .session import _PackedAdam, _Session, check_outcome, span_from_tie
 
 DEFAULT_JITTER = 1e-6
 
@@ -208,7 +209,7 @@ def _transform_code(p: Parameter) -> int:
     raise NotImplementedError(f"transform {t!r} is not supported by the device Adam step")
 
 
-class _SVGPTrainer:
+class _SVGPTrainer(_Session):
     """Device state of one SVGP optimize() call.
 
     Every trainable quantity lives in ONE packed fp64 buffer of constrained values
@@ -224,7 +225,8 @@ class _SVGPTrainer:
         """max_iters: the iterations this trainer runs; decay_steps (default max_iters): the
         CosineDecay length, whose schedule starts at step 0 for this trainer's first iteration."""
         self.model = model
-        self.eng = eng = Engine.get()
+        eng = Engine.get()
+        super().__init__(eng, max_iters, graph_chunk if graph else 0)
         dev = eng.device
         X, Y = data
         Xh = np.ascontiguousarray(np.asarray(X.cpu() if isinstance(X, torch.Tensor) else X, dtype=np.float64))
@@ -232,7 +234,6 @@ class _SVGPTrainer:
         if Yh.ndim == 1:
             Yh = Yh[:, None]
         self.klm = float(kl_multiplier)
-        self.max_iters = max(int(max_iters), 1)
         Zp = model.inducing_variable
         m, dp1 = Zp.shape
         d = dp1 - 1
@@ -256,21 +257,11 @@ class _SVGPTrainer:
             refs += [(k.kernel_delta.lengthscales, None if k.kernel_delta.lengthscales.shape == () else (i,))
                      for i in range(d)]
             refs += [(k.rho, (0, 0))]
-            seen = {}
-            for q, (prm, idx) in enumerate(refs):
-                cv, uv = prm.numpy(), prm.unconstrained_variable
-                tc[l, q] = float(cv if idx is None else cv[idx])
-                tu[l, q] = float(uv if idx is None else uv[idx])
-                tt[l, q] = prm.trainable
-                tf[l, q] = _transform_code(prm)
-                key = (id(prm), idx)
-                if key in seen:   # tied entry (isotropic lengthscale): follower of the first
-                    ts[l, q] = 0
-                    ts[l, seen[key]] += 1
-                else:
-                    seen[key] = q
-            tt[l, G - 1] = False   # noise slot of the theta layout is unused here
-            self._theta_refs.append(refs)
+            tc[l, :G - 1], tu[l, :G - 1] = gather_entries(refs, True), gather_entries(refs, False)
+            tt[l, :G - 1] = [prm.trainable for prm, _ in refs]
+            tf[l, :G - 1] = [_transform_code(prm) for prm, _ in refs]
+            ts[l, :G - 1] = span_from_tie(tie_entries(refs))   # an isotropic lengthscale ties its d entries
+            self._theta_refs.append(refs)   # the noise slot of the theta layout (G - 1) is unused here
         segs.append(("theta", (L, G), tc, tu, tt, tf, ts))
         qm = model.q_mu
         segs.append(("q_mu", (m, L), qm.numpy(), qm.unconstrained_variable, np.full((m, L), qm.trainable), 0, None))
@@ -300,24 +291,18 @@ class _SVGPTrainer:
             tfs.append(np.asarray(trf if isinstance(trf, np.ndarray) else np.full(size, trf), np.uint8).reshape(-1))
             sps.append(np.asarray(spn if spn is not None else np.ones(size), np.uint8).reshape(-1))
         self.n = off
-        self.stream = torch.cuda.Stream(dev)
         f64 = dict(dtype=torch.float64, device=dev)
-        with torch.cuda.stream(self.stream):
+        with self._ctx():
             self.X = torch.tensor(Xh, **f64)
             self.Y = torch.tensor(Yh, **f64)
-            self.c = torch.tensor(np.concatenate(cs), **f64)
-            self.u = torch.tensor(np.concatenate(us), **f64)
-            self.g = torch.zeros(self.n, **f64)
-            self.mo = torch.zeros(self.n, **f64)
-            self.vo = torch.zeros(self.n, **f64)
-            self.trainable = torch.tensor(np.concatenate(trs).astype(np.uint8), device=dev)
-            self.transform = torch.tensor(np.concatenate(tfs), device=dev)
-            self.span = torch.tensor(np.concatenate(sps), device=dev)
-            self.step_t = torch.zeros((1,), dtype=torch.int32, device=dev)
             decay = self.max_iters if decay_steps is None else int(decay_steps)
-            self.lr = torch.tensor(cosine_decay_schedule(initial_lr, decay, self.max_iters), **f64)
-            self.loss_hist = torch.zeros((self.max_iters,), **f64)
-            self.kl_hist = torch.zeros((self.max_iters,), **f64)
+            self.opt = _PackedAdam(dev, np.concatenate(us), np.concatenate(cs), np.concatenate(trs),
+                                   np.concatenate(tfs), np.concatenate(sps),
+                                   cosine_decay_schedule(initial_lr, decay, self.max_iters), kl_hist=True)
+            # the names the tools, the tests and bench.py read
+            self.c, self.u, self.trainable, self.step_t = self.opt.c, self.opt.u, self.opt.trainable, self.opt.step
+            self.lr, self.loss_hist, self.kl_hist = self.opt.lr, self.opt.hist, self.opt.kl_hist
+            self.g = torch.zeros(self.n, **f64)
             self.out = torch.zeros((3,), **f64)
             n = Xh.shape[0]
             self.g_mu = torch.empty((L, n), **f64)
@@ -326,9 +311,6 @@ class _SVGPTrainer:
             # owned by the trainer for the life of its graphs (not the engine's shared buffer)
             self.ws = eng.private_workspace(eng.svgp_grad_workspace_bytes(n, m, L, p, d))
         self.scale = (model.num_data / n) if model.num_data else 1.0
-        self.b1, self.b2 = float(np.float32(0.9)), float(np.float32(0.999))
-        self.done = 0
-        self.runner = _StepRunner(self._step, graph_chunk if graph else 0)
         if graph:   # size the workspace outside capture
             self.grad()
 
@@ -347,7 +329,7 @@ class _SVGPTrainer:
 
     def grad(self):
         """One gradient evaluation at the current parameters, ordered on the trainer's stream."""
-        with torch.cuda.stream(self.stream):
+        with self._ctx():
             self._grad()
 
     def _grad(self):
@@ -362,26 +344,14 @@ class _SVGPTrainer:
 
     def _step(self):
         self._grad()
-        self.eng.adam_packed(self.u, self.c, self.g, self.mo, self.vo, self.trainable, self.transform, self.span,
-                             self.step_t, self.lr, self.b1, self.b2, 1e-7, self.out, self.klm, self.loss_hist,
-                             self.kl_hist, info=self.info)
-
-    def run(self, n):
-        if self.done + n > self.max_iters:
-            raise ValueError("SVGP optimize: more iterations than max_iters")
-        with torch.cuda.stream(self.stream):
-            self.runner.run(n)
-        self.done += n
+        self.opt.apply(self.eng, self.g, self.out, self.klm, self.info)
 
     def set_trainable(self, name, flag):
         off, shape = self.layout[name]
-        with torch.cuda.stream(self.stream):
+        with self._ctx():
             self.trainable[off:off + int(np.prod(shape))] = int(bool(flag))
         if name == "noise":
             self.model.likelihood.variance.trainable = bool(flag)
-
-    def sync(self):
-        self.stream.synchronize()
 
     def elbo_now(self):
         """ELBO at the current parameters (one gradient evaluation, synchronised)."""
@@ -392,10 +362,6 @@ class _SVGPTrainer:
     def loss_at(self, i):
         self.sync()
         return float(self.loss_hist[i].item())
-
-    def close(self):
-        """Release the recorded step graphs now (a later run re-captures)."""
-        self.runner.close()
 
     def finish(self, reset_history=True):
         self.sync()
@@ -417,13 +383,7 @@ class _SVGPTrainer:
         model.likelihood.variance.unconstrained_variable = np.reshape(seg("noise"), model.likelihood.variance.shape)
         th = seg("theta")
         for l, refs in enumerate(self._theta_refs):
-            for q, (prm, idx) in enumerate(refs):
-                if idx is None:
-                    prm.unconstrained_variable = np.full(prm.shape, th[l, q])
-                else:
-                    arr = prm.unconstrained_variable.copy()
-                    arr[idx] = th[l, q]
-                    prm.unconstrained_variable = arr
+            scatter_entries(refs, th[l])
         h = self.loss_hist[:self.done].cpu().numpy()
         k = self.kl_hist[:self.done].cpu().numpy()
         if reset_history:
@@ -431,12 +391,8 @@ class _SVGPTrainer:
         model.loss_history.extend(np.float64(v) for v in h)
         if hasattr(model, "kl_history"):
             model.kl_history.extend(np.float64(v) for v in k)
-        steps = int(self.step_t.item())
-        if int(self.info.max().item()) != 0 or not np.all(np.isfinite(h)):
-            raise CholeskyError("SVGP optimize: Cholesky of K_uu failed")
-        if steps != self.done:
-            raise MFGPError(f"SVGP optimize: {self.done - steps} of {self.done} steps failed (Cholesky of K_uu) "
-                            f"and were retried; the trajectory is incomplete")
+        check_outcome("SVGP optimize", self.info.cpu().numpy(), int(self.step_t.item()), self.done, h, timeout=False,
+                      cause=" (Cholesky of K_uu)", chol="Cholesky of K_uu failed")
 
 
 class LatentMFCoregionalizationSVGP(_SVGPBase):

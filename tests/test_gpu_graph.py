@@ -102,6 +102,34 @@ def test_graph_adam_matches_oracle():
                                prm["rhoLF"].detach().numpy()[~np.eye(m, dtype=bool)], rtol=1e-8)
 
 
+def test_graph_session_prepare_then_run_is_bitwise_eager():
+    """The graph-model session's prepare() / run() (the shared session base): n = 48 (two 32-tiles,
+    the second padded), p = 2, d = 2, one LF source; 9 steps with graph_chunk = 4 are two replays of
+    the one captured 4-step graph and an eager remainder step (1 is below the capture threshold),
+    and give bit for bit the eager (graph=False) trajectory and parameters."""
+    from multi_fidelity_gpflow_amd.graph import _GraphAdamSession
+    m, D = 1, 2
+    X, Y = _data(m, D, P=2, sizes=(36, 12))
+    assert X.shape == (48, D + 1) and Y.shape == (48, 2)
+    ref = _model(X, Y, m, D, asym=False)
+    ref.optimize(max_iters=9, learning_rate=0.01, use_adam=True, graph=False)
+    mod = _model(X, Y, m, D, asym=False)
+    sess = _GraphAdamSession(mod, 0.01, 9, True, 4)
+    sess.prepare(9)
+    assert list(sess.runner.graphs) == [4]
+    sess.run(9)
+    sess.sync()
+    assert len(sess.runner.graphs) == 1 and sess.done == 9
+    sess.finish()
+    assert len(mod.loss_history) == 9
+    np.testing.assert_array_equal(np.array(mod.loss_history), np.array(ref.loss_history))
+    assert len(mod.parameters) == len(ref.parameters) > 0
+    for (name, a), b in zip(mod.parameters_with_names(), ref.parameters):
+        np.testing.assert_array_equal(a.unconstrained_variable, b.unconstrained_variable, err_msg=name)
+    assert not np.array_equal(mod.kernel.kernel_delta.lengthscales.unconstrained_variable,
+                              _model(X, Y, m, D, asym=False).kernel.kernel_delta.lengthscales.unconstrained_variable)
+
+
 def test_graph_predict_and_lbfgs():
     m, D = 2, 3
     X, Y = _data(m, D)
