@@ -85,6 +85,10 @@ int mfgp_get_tiny(mfgp_handle_t h);
  * caller guarantees that nothing else wrote the workspace in between (a training session's private
  * workspace); graphs captured in this mode replay that way.  Results are identical either way. */
 int mfgp_set_resident(mfgp_handle_t h, int enable);
+/* mfgp_gpr_adam_steps: defer each step's reduction into the next flow launch (default 1; 0, or
+ * MFGP_STEP_FUSION=0 in the environment at mfgp_create: a plain loop of single steps).  Same bits. */
+int mfgp_set_step_fusion(mfgp_handle_t h, int enable);
+int mfgp_get_step_fusion(mfgp_handle_t h);
 /* k_grad m-tiles per task (fixed at mfgp_create; env MFGP_GRAD_CHUNK).  Workspace sizes depend on it. */
 int mfgp_get_grad_chunk(mfgp_handle_t h);
 /* fp32 path (dtype MFGP_F32): iterative refinement with an fp64 residual for the value-only LML
@@ -153,6 +157,18 @@ int mfgp_gpr_adam_step(mfgp_handle_t h, int n, int p, int d, const double* X, in
                        double* theta, double* u, double* m, double* v, const unsigned char* trainable,
                        const int* tie, int* step, double lr, double beta1, double beta2, double eps,
                        double* loss_hist, void* ws, size_t ws_bytes, double* out, int* info);
+
+/* nsteps Adam steps in one call: when it returns to the stream, theta, u, m, v, *step, loss_hist,
+ * out and info are bit for bit what nsteps calls of mfgp_gpr_adam_step leave (a failed evaluation
+ * in the middle included: no step, NaN loss, and the next evaluation runs on the unchanged theta).
+ * Where the persistent flow forms its own Gram (fp64, 32-tiles, the flow on and taken at this
+ * size, not the one-launch small path, D <= 29) the reduction + Adam of every step but the last
+ * runs in the head of the next step's flow launch instead of a launch of its own
+ * (mfgp_set_step_fusion); everywhere else, and for nsteps == 1, the call is a loop of single steps. */
+int mfgp_gpr_adam_steps(mfgp_handle_t h, int n, int p, int d, const double* X, int ldx, const double* Y, int ldy,
+                        double* theta, double* u, double* m, double* v, const unsigned char* trainable,
+                        const int* tie, int* step, double lr, double beta1, double beta2, double eps,
+                        double* loss_hist, void* ws, size_t ws_bytes, double* out, int* info, int nsteps);
 
 /* Diagnostic: the mfgp_gpr_lml(want_grad=1) sequence with hipEvents recorded on
  * the handle's stream between its phases; synchronises and writes the elapsed

@@ -41,6 +41,7 @@ struct mfgp_handle_s {
     hipStream_t side;           // its high-priority side stream + fork / join events (created with the handle)
     hipEvent_t ev_fork, ev_join;
     int svgp_qs_packed;         // mfgp_set_svgp_qs_packed: mfgp_svgp_elbo_grad's q_sqrt / gq_sqrt as packed triangles
+    int step_fusion;            // mfgp_set_step_fusion: mfgp_gpr_adam_steps defers each step's reduction into the next flow launch
     int resident;               // mfgp_set_resident: fp64 value+grad flow calls may skip the set-up launch
     struct {                    // the last fp64 LML call on this handle, when it left its workspace set
         const void* ws;         // up for the next one (k_grad's grad_next_setup); ws == nullptr: none
@@ -315,6 +316,70 @@ struct PhaseMarks {
     void mark(hipStream_t s) { (void)hipEventRecord(ev[count++], s); }
 };
 
+// The argument blocks of one fp64 LML evaluation on the layout L (gpr_value_grad, gpr_adam_steps_fused)
+static FlowArgs flow_args(mfgp_handle_t h, const GprLayout& L, int n, int p, int d, const double* X, int ldx,
+                          const double* Y, int ldy, const double* theta, int* info, bool flow_gram) {
+    const long ldr = L.npad + L.ppad;
+    FlowArgs fa{};
+    fa.A = L.A; fa.lda = L.npad;
+    fa.R = L.R; fa.ldr = ldr;
+    fa.Xo = L.Xo; fa.ldx = ldr;
+    fa.Dd = L.Dd; fa.ldiag = L.ldiag; fa.info = info;
+    fa.alpha = L.alpha; fa.ldal = L.ppad; fa.zpart = L.zpart;
+    fa.flags = L.flags; fa.own = L.own; fa.pub = L.pub;
+    fa.T = L.T; fa.Tp = L.Tp; fa.n = n; fa.p = p;
+    fa.trace = h->flow_trace ? L.trace : nullptr;
+    fa.nwaves = FLOW_WAVES * (L.flow_wgs - 1);
+    fa.timeout = h->flow_timeout;
+    fa.X = X; fa.ldxi = ldx; fa.Y = Y; fa.ldy = ldy; fa.theta = theta; fa.D = d;
+    fa.gram = flow_gram ? 1 : 0;
+    return fa;
+}
+static GradArgs grad_args(const GprLayout& L, int n, int p, int d, const double* X, int ldx, const double* theta,
+                          int nlf, bool leaves_setup) {
+    GradArgs ga{L.Xo, (long)L.npad + L.ppad, X, (long)ldx, theta, L.gpart, L.gstride, L.T, L.Tp, n, p, d,
+                L.gchunk, nlf, L.gchunk + L.T + L.Tp < 2048 ? L.gorder : nullptr};
+    if (leaves_setup) {   // the next evaluation's set-up, after the flow
+        ga.fpub = L.pub; ga.npub = L.npub;
+        ga.isent = L.items; ga.nisent = L.G + 2;
+    }
+    return ga;
+}
+static FinArgs fin_args(const GprLayout& L, int n, int p, int d, int want_grad, double* out, int* info,
+                        const FinArgs* adam) {
+    FinArgs f{};
+    if (adam) f = *adam;
+    f.zpart = L.zpart; f.nz = L.T * L.Tp;
+    f.ldiag = L.ldiag; f.n = n;
+    f.gpart = L.gpart; f.ng = L.ng; f.gstride = L.gstride;
+    f.info = info; f.P = p; f.D = d; f.want_grad = want_grad;
+    f.out = out;
+    f.adam = adam != nullptr;
+    f.items = L.items;
+    f.G = L.G;
+    f.cnt = L.cnt;
+    f.flag = MFGP_REDUCE_FLAG;   // the Gram / set-up launch (or the previous k_grad) filled items[] with the sentinel
+    f.abortw = L.flow_wgs ? L.flags : nullptr;
+    return f;
+}
+// the set-up launch in front of an AR1 flow evaluation (sentinel fill, schedule tables, item slots)
+static GramArgs prep_args(const GprLayout& L, int n, int p, int d, const double* X, int ldx, const double* Y,
+                          int ldy, const double* theta, int* info, int nlf, bool order) {
+    GramArgs g{};
+    g.R = L.R; g.ldr = (long)L.npad + L.ppad; g.sR = 0; g.Y = Y; g.ldy = ldy; g.sY = 0; g.p = p; g.ppad = L.ppad;
+    g.X1 = X; g.ldx1 = ldx; g.sx1 = 0; g.n1 = n;
+    g.X2 = X; g.ldx2 = ldx; g.sx2 = 0; g.n2 = n;
+    g.theta = theta; g.stheta = 0; g.D = d; g.rbf_only = 0;
+    g.out = L.A; g.ldo = L.npad; g.so = 0;
+    g.padded = 1; g.npad = L.npad; g.tiles_c = L.T; g.add_noise = 1; g.diag_add = nlf ? GRAPH_JITTER : 0.0;
+    g.Dd = L.Dd; g.sD = 0; g.ldiag = L.ldiag; g.sL = 0; g.info = info; g.nlf = nlf;
+    g.cnt = L.cnt; g.ncnt = L.ncnt;
+    if (MFGP_REDUCE_FLAG) { g.isent = L.items; g.nisent = L.G + 2; }
+    if (order) { g.gorder = L.gorder; g.gT = L.T; g.gchunk = L.gchunk; g.gTp = L.Tp; }
+    if (L.flow_wgs) { g.fown = L.own; g.fW = FLOW_WAVES * (L.flow_wgs - 1); g.fflags = L.flags; g.nfflags = L.nflags; g.fpub = L.pub; g.npub = L.npub; }
+    return g;
+}
+
 template <int NB>
 static int gpr_value_grad(mfgp_handle_t h, int n, int p, int d, const double* X, int ldx, const double* Y, int ldy,
                           double* theta, int want_grad, void* ws, size_t ws_bytes, double* out, int* info,
@@ -352,19 +417,8 @@ static int gpr_value_grad(mfgp_handle_t h, int n, int p, int d, const double* X,
                            h->res.d == d && h->res.flow_wgs == L.flow_wgs;
     h->res.ws = nullptr;
     if (!skip_prep) {
-        GramArgs g{};
-        g.R = L.R; g.ldr = ldr; g.sR = 0; g.Y = Y; g.ldy = ldy; g.sY = 0; g.p = p; g.ppad = L.ppad;
-        g.X1 = X; g.ldx1 = ldx; g.sx1 = 0; g.n1 = n;
-        g.X2 = X; g.ldx2 = ldx; g.sx2 = 0; g.n2 = n;
-        g.theta = theta; g.stheta = 0; g.D = d; g.rbf_only = 0;
-        g.out = L.A; g.ldo = L.npad; g.so = 0;
-        g.padded = 1; g.npad = L.npad; g.tiles_c = L.T; g.add_noise = 1; g.diag_add = nlf ? GRAPH_JITTER : 0.0;
-        g.Dd = L.Dd; g.sD = 0; g.ldiag = L.ldiag; g.sL = 0; g.info = info; g.nlf = nlf;
-        g.cnt = L.cnt; g.ncnt = L.ncnt;
-        if (MFGP_REDUCE_FLAG) { g.isent = L.items; g.nisent = L.G + 2; }
         const bool order = want_grad && L.gchunk + L.T + L.Tp < 2048;   // gram LDS holds the histogram
-        if (order) { g.gorder = L.gorder; g.gT = L.T; g.gchunk = L.gchunk; g.gTp = L.Tp; }
-        if (L.flow_wgs) { g.fown = L.own; g.fW = FLOW_WAVES * (L.flow_wgs - 1); g.fflags = L.flags; g.nfflags = L.nflags; g.fpub = L.pub; g.npub = L.npub; }
+        GramArgs g = prep_args(L, n, p, d, X, ldx, Y, ldy, theta, info, nlf, order);
         const int extra = (order ? 1 : 0) + (L.flow_wgs ? 1 : 0);
         if (flow_gram) {
             launch_flow_prep(g, std::max(h->ncu, 2) + extra, s);
@@ -376,20 +430,7 @@ static int gpr_value_grad(mfgp_handle_t h, int n, int p, int d, const double* X,
     }
     if (pm) pm->mark(s);
     if (L.flow_wgs) {
-        FlowArgs fa{};
-        fa.A = L.A; fa.lda = L.npad;
-        fa.R = L.R; fa.ldr = ldr;
-        fa.Xo = L.Xo; fa.ldx = ldr;
-        fa.Dd = L.Dd; fa.ldiag = L.ldiag; fa.info = info;
-        fa.alpha = L.alpha; fa.ldal = L.ppad; fa.zpart = L.zpart;
-        fa.flags = L.flags; fa.own = L.own; fa.pub = L.pub;
-        fa.T = L.T; fa.Tp = L.Tp; fa.n = n; fa.p = p;
-        fa.trace = h->flow_trace ? L.trace : nullptr;
-        fa.nwaves = FLOW_WAVES * (L.flow_wgs - 1);
-        fa.timeout = h->flow_timeout;
-        fa.X = X; fa.ldxi = ldx; fa.Y = Y; fa.ldy = ldy; fa.theta = theta; fa.D = d;
-        fa.gram = flow_gram ? 1 : 0;
-        launch_chol_flow(fa, L.flow_wgs, s);
+        launch_chol_flow(flow_args(h, L, n, p, d, X, ldx, Y, ldy, theta, info, flow_gram), L.flow_wgs, s);
         fence.commit(s);
     } else {
         CholArgs c{};
@@ -403,34 +444,62 @@ static int gpr_value_grad(mfgp_handle_t h, int n, int p, int d, const double* X,
     }
     if (pm) pm->mark(s);
     if (want_grad) {
-        GradArgs ga{L.Xo, ldr, X, (long)ldx, theta, L.gpart, L.gstride, L.T, L.Tp, n, p, d,
-                    L.gchunk, nlf, L.gchunk + L.T + L.Tp < 2048 ? L.gorder : nullptr};
-        if (leaves_setup) {   // the next evaluation's set-up, after the flow
-            ga.fpub = L.pub; ga.npub = L.npub;
-            ga.isent = L.items; ga.nisent = L.G + 2;
-        }
-        launch_grad<NB>(ga, s);
+        launch_grad<NB>(grad_args(L, n, p, d, X, ldx, theta, nlf, leaves_setup), s);
     }
     if (pm) pm->mark(s);
-    FinArgs f{};
-    if (adam) f = *adam;
-    f.zpart = L.zpart; f.nz = L.T * L.Tp;
-    f.ldiag = L.ldiag; f.n = n;
-    f.gpart = L.gpart; f.ng = L.ng; f.gstride = L.gstride;
-    f.info = info; f.P = p; f.D = d; f.want_grad = want_grad;
-    f.out = out;
-    f.adam = adam != nullptr;
-    f.items = L.items;
-    f.G = L.G;
-    f.cnt = L.cnt;
-    f.flag = MFGP_REDUCE_FLAG;   // the Gram / set-up launch (or the previous k_grad) filled items[] with the sentinel
-    f.abortw = L.flow_wgs ? L.flags : nullptr;
+    const FinArgs f = fin_args(L, n, p, d, want_grad, out, info, adam);
     hipLaunchKernelGGL(k_reduce_items, dim3(2 + (want_grad ? L.G : 0)), dim3(NTHREADS), 0, s, f);
     if (pm) pm->mark(s);
     if (last() != hipSuccess) return MFGP_ERR_LAUNCH;
     if (leaves_setup) {
         h->res.ws = ws; h->res.n = n; h->res.p = p; h->res.d = d; h->res.flow_wgs = L.flow_wgs;
     }
+    return MFGP_OK;
+}
+
+// Whether mfgp_gpr_adam_steps may defer the step reduction into the next flow launch: only where
+// the flow forms its own Gram (the AR1 kernel, 32-tiles, the flow on and taken at this size, not
+// the one-launch tiny path) and one wave holds every item (flow_head_diag).
+static bool adam_steps_fusable(mfgp_handle_t h, int n, int p, int d) {
+    if (!h->step_fusion || h->nb != 32 || !MFGP_REDUCE_FLAG) return false;
+    if (h->tiny && gpr_tiny_fits(n, p, d, 0)) return false;
+    const GprLayout L = gpr_layout(32, n, p, d, nullptr, h->grad_chunk, 0, h->flow_wgs, h->flow_min_t);
+    return L.flow_wgs != 0 && L.G <= FLOW_HEAD_MAXG;
+}
+
+// nsteps Adam steps as [set-up if not resident] flow, grad, flow*, grad, ..., flow*, grad,
+// k_reduce_items: flow* (FlowArgs::head) finishes the previous step in its head phase, so only the
+// last step pays for the reduction launch.  The fence is taken once; h->res is left as after a
+// single step.  Bitwise the results of nsteps mfgp_gpr_adam_step calls.
+static int gpr_adam_steps_fused(mfgp_handle_t h, int n, int p, int d, const double* X, int ldx, const double* Y,
+                                int ldy, double* theta, void* ws, size_t ws_bytes, double* out, int* info,
+                                const FinArgs* adam, int nsteps) {
+    const GprLayout L = gpr_layout(32, n, p, d, ws, h->grad_chunk, 0, h->flow_wgs, h->flow_min_t);
+    if (ws_bytes < L.bytes) return MFGP_ERR_WORKSPACE;
+    hipStream_t s = h->stream;
+    FenceTurn fence(h->device, s);
+    if (fence.rc != MFGP_OK) return fence.rc;
+    const bool skip_prep = h->resident && h->res.ws == ws && h->res.n == n && h->res.p == p && h->res.d == d &&
+                           h->res.flow_wgs == L.flow_wgs;
+    h->res.ws = nullptr;
+    if (!skip_prep) {
+        const bool order = L.gchunk + L.T + L.Tp < 2048;
+        launch_flow_prep(prep_args(L, n, p, d, X, ldx, Y, ldy, theta, info, 0, order),
+                         std::max(h->ncu, 2) + (order ? 1 : 0) + 1, s);
+    }
+    const FinArgs f = fin_args(L, n, p, d, 1, out, info, adam);
+    FlowArgs fa = flow_args(h, L, n, p, d, X, ldx, Y, ldy, theta, info, true);
+    const GradArgs ga = grad_args(L, n, p, d, X, ldx, theta, 0, true);
+    for (int t = 0; t < nsteps; ++t) {
+        fa.head = t > 0;
+        if (fa.head) fa.fin = f;
+        launch_chol_flow(fa, L.flow_wgs, s);
+        if (t == nsteps - 1) fence.commit(s);
+        launch_grad<32>(ga, s);
+    }
+    hipLaunchKernelGGL(k_reduce_items, dim3(2 + L.G), dim3(NTHREADS), 0, s, f);
+    if (last() != hipSuccess) return MFGP_ERR_LAUNCH;
+    h->res.ws = ws; h->res.n = n; h->res.p = p; h->res.d = d; h->res.flow_wgs = L.flow_wgs;
     return MFGP_OK;
 }
 
@@ -816,6 +885,8 @@ int mfgp_create(int device, mfgp_handle_t* out) {
     }
     if (const char* fp = getenv("MFGP_F32_PANEL")) h->f32_panel = std::max(1, atoi(fp));
     if (const char* fl = getenv("MFGP_FLOW")) if (atoi(fl) == 0) h->flow_wgs = 0;
+    h->step_fusion = 1;
+    if (const char* sf = getenv("MFGP_STEP_FUSION")) h->step_fusion = atoi(sf) != 0;
     if (const char* gc = getenv("MFGP_GRAD_CHUNK")) h->grad_chunk = std::max(1, atoi(gc));
     const char* env = getenv("MFGP_TILE");
     if (env && atoi(env) == 64) h->nb = 64;
@@ -889,6 +960,14 @@ int mfgp_set_tiny(mfgp_handle_t h, int enable) {
 }
 
 int mfgp_get_tiny(mfgp_handle_t h) { return h ? h->tiny : MFGP_ERR_ARG; }
+
+int mfgp_set_step_fusion(mfgp_handle_t h, int enable) {
+    CHECK_H(h);
+    h->step_fusion = enable != 0;
+    return MFGP_OK;
+}
+
+int mfgp_get_step_fusion(mfgp_handle_t h) { return h ? h->step_fusion : 0; }
 
 int mfgp_set_resident(mfgp_handle_t h, int enable) {
     if (!h) return MFGP_ERR_ARG;
@@ -1051,6 +1130,31 @@ int mfgp_gpr_adam_step(mfgp_handle_t h, int n, int p, int d, const double* X, in
     f.noise_index = theta_size(d) - 1;
     if (h->nb == 64) return gpr_value_grad<64>(h, n, p, d, X, ldx, Y, ldy, theta, 1, ws, ws_bytes, out, info, &f);
     return gpr_value_grad<32>(h, n, p, d, X, ldx, Y, ldy, theta, 1, ws, ws_bytes, out, info, &f);
+}
+
+int mfgp_gpr_adam_steps(mfgp_handle_t h, int n, int p, int d, const double* X, int ldx, const double* Y, int ldy,
+                        double* theta, double* u, double* m, double* v, const unsigned char* trainable,
+                        const int* tie, int* step, double lr, double beta1, double beta2, double eps,
+                        double* loss_hist, void* ws, size_t ws_bytes, double* out, int* info, int nsteps) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nsteps < 0) return MFGP_ERR_ARG;
+    if (n < 1 || p < 1 || !X || !Y || !theta || !u || !m || !v || !trainable || !step || !loss_hist || !ws ||
+        !out || !info)
+        return MFGP_ERR_ARG;
+    if (nsteps > 1 && adam_steps_fusable(h, n, p, d)) {
+        FinArgs f{};
+        f.theta = theta; f.u = u; f.m = m; f.v = v; f.trainable = trainable; f.tie = tie; f.step = step;
+        f.lr = lr; f.b1 = beta1; f.b2 = beta2; f.eps = eps; f.loss_hist = loss_hist;
+        f.noise_index = theta_size(d) - 1;
+        return gpr_adam_steps_fused(h, n, p, d, X, ldx, Y, ldy, theta, ws, ws_bytes, out, info, &f, nsteps);
+    }
+    for (int t = 0; t < nsteps; ++t) {   // the plain loop of single steps
+        const int rc = mfgp_gpr_adam_step(h, n, p, d, X, ldx, Y, ldy, theta, u, m, v, trainable, tie, step, lr,
+                                          beta1, beta2, eps, loss_hist, ws, ws_bytes, out, info);
+        if (rc != MFGP_OK) return rc;
+    }
+    return MFGP_OK;
 }
 
 int mfgp_gpr_lml_phase_times(mfgp_handle_t h, int n, int p, int d, const double* X, int ldx, const double* Y,

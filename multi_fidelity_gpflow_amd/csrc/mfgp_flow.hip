@@ -38,6 +38,7 @@
 #include "mfgp_device.h"
 #include "mfgp_internal.h"
 #include "mfgp_flow.h"
+#include "mfgp_reduce.h"
 
 namespace mfgp {
 
@@ -812,7 +813,7 @@ struct DiagLds {
     static constexpr size_t BYTES = sizeof(double) * (10 * E + 32 * 33 + 64 + 16);
 };
 static_assert(DiagLds::BYTES <= FLOW_LDS_BYTES, "diag workgroup LDS carve");
-enum { DW_LS = 0, DW_D, DW_LPUB, DW_DPUB, DW_PRE6, DW_PRE7, DW_BAR, DW_L2, DW_P2, DW_G0, DW_N };
+enum { DW_LS = 0, DW_D, DW_LPUB, DW_DPUB, DW_PRE6, DW_PRE7, DW_BAR, DW_L2, DW_P2, DW_G0, DW_TH, DW_N };
 static_assert(DW_N <= 28, "progress words fit in the carve");
 
 __device__ __forceinline__ int lds_get(const int* p) {
@@ -1088,11 +1089,11 @@ __device__ __forceinline__ void diag_prefetch(FlowCtx& C, const DiagLds& B, bool
 // dots 1.2, norms 0.6, exp and stores ~1.5), D_0 at ~10-12 us (the first factor runs with a cold
 // instruction cache: ~5 us against ~3.9 in the chain); the base build's chain started at 2.4 us
 // with D_0 from the Gram launch before it.
-__device__ __forceinline__ void diag_gram_phase(const FlowArgs& a, const DiagLds& B, long long t0) {
+__device__ __forceinline__ void diag_gram_phase(const FlowArgs& a, const DiagLds& B, long long t0, const double* th) {
     constexpr int S = TileCfg<32>::S;
     const int w = threadIdx.x >> 6, T = a.T;
     auto tile = [&](int i, int j, double* dst, int ld, int b0, int b1) {
-        flow_gram_tile<false>(a.X, a.ldxi, a.theta, a.n, a.D, i, j, dst, ld, b0, b1);
+        flow_gram_tile<false>(a.X, a.ldxi, th, a.n, a.D, i, j, dst, ld, b0, b1);
     };
     auto signal = [&](int word, int v) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1100,7 +1101,7 @@ __device__ __forceinline__ void diag_gram_phase(const FlowArgs& a, const DiagLds
     };
     if (w < 2 || w == 4) {
         // the factor reads the lower blocks only: (0,0) wave 0, (1,0) wave 4, (1,1) wave 1
-        flow_gram_tile<false>(a.X, a.ldxi, a.theta, a.n, a.D, 0, 0, B.fsc(), 33, w == 0 ? 0 : 1, w == 0 ? 1 : 2,
+        flow_gram_tile<false>(a.X, a.ldxi, th, a.n, a.D, 0, 0, B.fsc(), 33, w == 0 ? 0 : 1, w == 0 ? 1 : 2,
                               w == 1 ? 2 : 1);
         if (w != 0) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1117,15 +1118,175 @@ __device__ __forceinline__ void diag_gram_phase(const FlowArgs& a, const DiagLds
     }
 }
 
+// ---------------------------------------------------------------- the head phase
+// FlowArgs::head (mfgp_gpr_adam_steps): the launch of step t first finishes step t-1 -- what
+// k_reduce_items does between two single steps -- and only then forms its Gram, on the new theta.
+//   * item sums: worker workgroup b sums item b - 1 of [sum Z^2, sum log L_ii, grad_0 .. grad_{G-1}]
+//     (one item per CU) and stores it to its sentinel slot, as an item workgroup of k_reduce_items
+//     does.  Its waves 0-3 are that workgroup's four waves (reduce_item_thread, wave_sum, then
+//     block_sum's (r0 + r1) + (r2 + r3)): the same sums in the same order, bit for bit.  (One
+//     wave playing all four in turn made the launch 15.6 us longer: the 32 logs per lane of
+//     item 1 alone are ~8 us.)
+//   * finalize: wave 0 of the diag workgroup loads the Adam state, step, ties, info and the abort
+//     word, then polls the slots (bounded, REDUCE_TIMEOUT_TICKS) and runs finalize_from.  theta
+//     goes to the diag workgroup's LDS (DW_TH) and, sc1, to the theta slot at the end of the
+//     publication area, which k_grad's tail re-sentinels with the rest of it.
+//   * every other workgroup: its last wave polls the theta slot (bounded like every hand-off;
+//     expiry raises the abort word) and passes theta on through LDS.
+// Before a wave waits for theta it has read its owner-table entries and touched the X rows /
+// fidelity flags of its first Gram tile and the Y block of its first Z tile, so the
+// theta-independent part of the launch's start-up runs under the reduction.
+// Hazards: zpart / ldiag (this launch) and gpart (the next k_grad) of step t-1 are rewritten only
+// by work that has read theta_new, which exists only after every item has been summed -- unless
+// the finalizer's poll expired, and then step t-1 has failed already (NaN loss, no Adam step) and
+// a late item sum is stored to a slot that nobody reads before k_grad's tail refills it.
+constexpr int HEAD_LDS_D = 64 + 72 + 32;   // diag: theta | gsh | tsh (doubles), behind DiagLds
+static_assert(DiagLds::BYTES + sizeof(double) * HEAD_LDS_D <= FLOW_LDS_BYTES, "head phase LDS (diag)");
+static_assert(sizeof(double) * (FLOW_WAVES * 32 * WLD + 64 + 2 + 4) <= FLOW_LDS_BYTES, "head phase LDS (workers)");
+static_assert(FLOW_HEAD_MAXG + 2 <= 64, "one lane per item");
+__device__ __forceinline__ long flow_theta_slot(int T, int Tp) {
+    return 1024L * (T * (T - 1) / 2 + T + T * (T + 1) / 2 + T * Tp + 3 * T);
+}
+__device__ __forceinline__ void head_touch(double v) { asm volatile("" ::"v"(v)); }
+// the lines of X rows 32 ti .. and 32 tj .. (first and last column: a row spans at most two lines)
+__device__ __forceinline__ void head_touch_x(const FlowArgs& a, int ti, int tj) {
+    const int l = threadIdx.x & 63;
+    const long row = min(32 * (l < 32 ? ti : tj) + (l & 31), a.n - 1);
+    head_touch(a.X[row * a.ldxi]);
+    head_touch(a.X[row * a.ldxi + a.D]);
+}
+
+__device__ __forceinline__ void flow_head_worker(const FlowArgs& a, double* smem) {
+    const FinArgs& f = a.fin;
+    const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int G = f.G;
+    double* thl = smem + FLOW_WAVES * 32 * WLD;
+    int* word = reinterpret_cast<int*>(thl + 64);
+    if (threadIdx.x == 0) *word = 0;
+    __syncthreads();
+    // item sums (the loop is uniform over the workgroup)
+    double* red = thl + 66;
+    const int nwk = (int)gridDim.x - 1;
+    for (int it = (int)blockIdx.x - 1; it < G + 2; it += nwk) {
+        if (w < 4) {
+            const double r = wave_sum(reduce_item_thread(f, it, threadIdx.x));
+            if (l == 0) red[w] = r;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) st_coherent(f.items + it, (red[0] + red[1]) + (red[2] + red[3]));
+        __syncthreads();
+    }
+    // start-up under the wait
+    {
+        const int* own = a.own + ((blockIdx.x - 1) * FLOW_WAVES + w) * FLOW_MAXOWN;
+        bool gx = false, gy = false;
+#pragma unroll 1
+        for (int s = 0; s < FLOW_MAXOWN; ++s) {
+            const int code = __builtin_amdgcn_readfirstlane(own[s]);
+            if (code < 0) continue;
+            const FlowTile t = flow_tile(code, a.T);
+            if ((t.type == FT_A || t.type == FT_G) && !gx) {
+                head_touch_x(a, t.i, t.j);
+                gx = true;
+            }
+            if (t.type == FT_R && t.j >= a.T && !gy) {
+                const int row = min(32 * t.i + (l & 31), a.n - 1), col = min(32 * (t.j - a.T) + 16 * (l >> 5), a.p - 1);
+                head_touch(a.Y[(long)row * a.ldy + col]);
+                gy = true;
+            }
+        }
+    }
+    // theta
+    if (w == FLOW_WAVES - 1) {
+        const double* slot = a.pub + flow_theta_slot(a.T, a.Tp);
+        const long long t0 = flow_clock();
+        double v = 0.0;
+        for (int spin = 0;; ++spin) {
+            v = l < G ? ld_coherent(slot + l) : 0.0;
+            if (__ballot(is_sent(v)) == 0) break;
+            if ((spin & 7) == 7 && flow_give_up(a.flags, a.info, t0, a.timeout)) break;
+            __builtin_amdgcn_s_sleep(FLOW_SLEEP);
+        }
+        thl[l] = v;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if (l == 0) lds_put(word, 1);
+    } else {
+        lds_wait_ge(word, 1);
+    }
+}
+
+// wave 0 of the diag workgroup finalizes; waves 1-7 touch their first Gram tile's rows and wait
+__device__ __forceinline__ void flow_head_diag(const FlowArgs& a, const DiagLds& B, double* thl) {
+    const FinArgs& f = a.fin;
+    const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (w != 0) {
+        if (w == 1 || w == 4) head_touch_x(a, 0, 0);
+        else if (w < 4) head_touch_x(a, 1, w - 2);
+        else head_touch_x(a, 2, w - 5);
+        lds_wait_ge(&B.w()[DW_TH], 1);
+        return;
+    }
+    const int G = f.G;
+    double* gsh = thl + 64;
+    int* tsh = reinterpret_cast<int*>(gsh + 72);
+    FinPre pre{0.0, 0.0, 0.0, 0};
+    if (f.adam && l < G) {
+        pre.tr = f.trainable[l];
+        pre.u = f.u[l];
+        pre.m = f.m[l];
+        pre.v = f.v[l];
+        if (f.tie) tsh[l] = f.tie[l];
+    }
+    if (l < G) thl[l] = f.theta[l];   // entries the step leaves alone (not trainable; a failed step)
+    int info0 = f.info[0];            // of step t-1: read before this evaluation's info = 0 below
+    const int s = f.adam ? *f.step : 0;
+    const int aborted = f.abortw ? __hip_atomic_load(f.abortw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+    head_touch_x(a, 0, 0);
+    if (f.adam) {   // what the step does not need the sums for, while they are on their way
+        pre.alpha = adam_alpha(f, s);
+        pre.den = adam_den(pre.u);
+        pre.ready = 1;
+    }
+    int tmo = 0;
+    double v = 0.0;
+    const long long t0 = flow_clock();
+    for (;;) {
+        v = l < G + 2 ? ld_coherent(f.items + l) : 0.0;
+        if (__ballot(is_sent(v)) == 0) break;
+        if (flow_clock() - t0 > REDUCE_TIMEOUT_TICKS) { tmo = 1; break; }
+        __builtin_amdgcn_s_sleep(1);
+    }
+    if (l < G + 2) gsh[l] = is_sent(v) ? NAN : v;
+    fin_group_sync<64>();
+    if ((tmo && info0 == 0) || aborted) {
+        info0 = MFGP_FLOW_TIMEOUT;
+        if (l == 0) const_cast<int*>(f.info)[0] = MFGP_FLOW_TIMEOUT;
+    }
+    if (f.abortw && l == 0 && aborted) __hip_atomic_store(f.abortw, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    finalize_from<64>(f, G, gsh, tsh, info0, s, &pre, l, thl);
+    fin_group_sync<64>();
+    double* slot = a.pub + flow_theta_slot(a.T, a.Tp);
+    if (l < G) st_coherent(slot + l, thl[l]);
+    if (l == 0) a.info[0] = 0;   // first writer of info in the new evaluation
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (l == 0) lds_put(&B.w()[DW_TH], 1);
+}
+
 __device__ __forceinline__ void flow_diag(FlowCtx& C, double* smem) {
     DiagLds B;
     B.base = smem;
     if (threadIdx.x < DW_N)
         B.w()[threadIdx.x] = (threadIdx.x == DW_LPUB || threadIdx.x == DW_DPUB || threadIdx.x == DW_D) ? -1 : 0;
     if (threadIdx.x < 2) B.bad()[threadIdx.x] = 0;
-    if (threadIdx.x == 0) C.a.info[0] = 0;   // first writer of info in the evaluation
+    if (threadIdx.x == 0 && !C.a.head) C.a.info[0] = 0;   // first writer of info in the evaluation
     __syncthreads();
-    if (C.a.gram) diag_gram_phase(C.a, B, C.t0);
+    const double* th = C.a.theta;
+    if (C.a.head) {
+        double* thl = smem + DiagLds::BYTES / sizeof(double);
+        flow_head_diag(C.a, B, thl);
+        th = thl;
+    }
+    if (C.a.gram) diag_gram_phase(C.a, B, C.t0, th);
     const int w = threadIdx.x >> 6;
     if (w < 4) diag_chain(C, B);
     else if (w == 4) diag_publisher(C, B);
@@ -1142,7 +1303,7 @@ __device__ __forceinline__ void flow_diag(FlowCtx& C, double* smem) {
 // waves 0 / 5 / 6 / 7 (two or three each) delayed the chain's start by ~25 us a launch; the eight
 // as FT_G worker tiles, ~9.5 us (published ~11 us into the launch: their waves share SIMDs with
 // waves forming their own tiles).
-__device__ __forceinline__ void flow_gram_phase(const FlowArgs& a) {
+__device__ __forceinline__ void flow_gram_phase(const FlowArgs& a, const double* th) {
     const int w = threadIdx.x >> 6;
     {
         const int* own = a.own + ((blockIdx.x - 1) * FLOW_WAVES + w) * FLOW_MAXOWN;
@@ -1152,10 +1313,10 @@ __device__ __forceinline__ void flow_gram_phase(const FlowArgs& a) {
             if (code < 0) continue;
             const FlowTile t = flow_tile(code, a.T);
             double* at = a.A + (long)t.i * 32 * a.lda + (long)t.j * 32;
-            if (t.type == FT_A) flow_gram_tile<false>(a.X, a.ldxi, a.theta, a.n, a.D, t.i, t.j, at, a.lda);
+            if (t.type == FT_A) flow_gram_tile<false>(a.X, a.ldxi, th, a.n, a.D, t.i, t.j, at, a.lda);
             if (t.type == FT_G) {
                 const FlowPub P{a.pub, a.T, a.Tp};
-                flow_gram_tile<true>(a.X, a.ldxi, a.theta, a.n, a.D, t.i, t.j,
+                flow_gram_tile<true>(a.X, a.ldxi, th, a.n, a.D, t.i, t.j,
                                      P.H(t.j == t.i ? 1 : t.j == t.i - 1 ? 0 : 2, t.i), 32);
             }
         }
@@ -1168,7 +1329,14 @@ __global__ __launch_bounds__(FLOW_THREADS) void k_chol_flow(FlowArgs a) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     FlowCtx C;
     C.t0 = flow_clock();
-    if (a.gram && blockIdx.x != 0) flow_gram_phase(a);
+    if (blockIdx.x != 0) {
+        const double* th = a.theta;
+        if (a.head) {   // the previous step's reduction first; theta arrives in LDS
+            flow_head_worker(a, smem);
+            th = smem + FLOW_WAVES * 32 * WLD;
+        }
+        if (a.gram) flow_gram_phase(a, th);
+    }
     C.a = a;
     C.P.base = a.pub;
     C.P.T = a.T;
@@ -1181,7 +1349,8 @@ __global__ __launch_bounds__(FLOW_THREADS) void k_chol_flow(FlowArgs a) {
     flow_worker(C, (blockIdx.x - 1) * FLOW_WAVES + w, smem + w * 32 * WLD);
 }
 
-long flow_npub(int T, int Tp) { return 1024L * (T * (T - 1) / 2 + T + T * (T + 1) / 2 + T * Tp + 3 * T); }
+// the tiles, then the head phase's theta slot (flow_theta_slot)
+long flow_npub(int T, int Tp) { return 1024L * (T * (T - 1) / 2 + T + T * (T + 1) / 2 + T * Tp + 3 * T) + 64; }
 int flow_nflags(int T, int Tp) { (void)T; (void)Tp; return 1; }   // the abort word
 // layout: chain / helper stamps [8T] | worker summaries + item logs | wave-5 detail [2T] | wave-6 / 7 detail
 // [2T each: last waits done, published] | k_gram timeline [flow_gram_dbg_count(T)] (the last region)

@@ -37,6 +37,37 @@ struct GramArgs {
     int tile_wgs;
 };
 
+constexpr int FIN_MAXG = 254;   // theta entries finalize_body stages in LDS (graph kernel: <= 186)
+// k_reduce_items' sentinel protocol (FinArgs::flag) on the fp64 LML path; 0: arrival counter
+#ifndef MFGP_REDUCE_FLAG
+#define MFGP_REDUCE_FLAG 1
+#endif
+struct FinArgs {
+    const double* zpart; int nz;
+    const double* ldiag; int n;
+    const double* gpart; int ng; int gstride;
+    const int* info;
+    int P, D, want_grad;
+    double* out;                      // [lml, grad(G)]
+    // Adam (optional, unconstrained parameters)
+    int adam;
+    double* theta;                    // constrained theta, refreshed after the step
+    double* u; double* m; double* v;
+    const unsigned char* trainable;
+    const int* tie;                   // tie[q]: entries sharing one variable (isotropic lengthscales)
+    int* step;
+    double lr, b1, b2, eps;
+    double* loss_hist;                // loss_hist[step] = -lml (pre-step)
+    int noise_index;                  // theta entry using Shift(1e-6) o Softplus
+    double* items;                    // [2 + G] stage-1 reduction results
+    int G;                            // theta entries (kernel_theta_size)
+    int* cnt;                         // arrival counter (zero on entry): last item workgroup finalizes
+    int flag;                         // 1: items[] hold FLOW_SENTINEL on entry (the Gram launch filled them):
+                                      //    workgroup 0 finalizes once every other item is published
+    int* abortw;                      // flow path: k_chol_flow's abort word -- set: the evaluation timed
+                                      // out (info := MFGP_FLOW_TIMEOUT); workgroup 0 zeroes it for the next
+};
+
 // k_chol_flow (mfgp_flow.hip): persistent dataflow Cholesky + L^{-1} + Z + alpha, NB = 32, batch 1
 constexpr int FLOW_MAXOWN = 4;                      // tiles per worker wave
 constexpr int FLOW_WAVES = 8;                       // waves per workgroup (two per SIMD)
@@ -71,7 +102,15 @@ struct FlowArgs {
     int D;
     int gram;                     // 1: the AR1 Gram formed in the launch; 0: A holds K + s2 I already
                                   // (the graph kernel's k_gram ran first)
+    // Head phase (mfgp_gpr_adam_steps; flow_head_worker / flow_head_diag): head = 1 -> the launch first
+    // finishes the PREVIOUS Adam step from fin (item sums, finalize, theta refresh) in place of
+    // that step's k_reduce_items, then runs as usual on the new theta.  head = 0: fin is unused.
+    int head;
+    FinArgs fin;
 };
+// the head phase takes at most this many theta entries (its theta slot is the last 64 doubles of
+// the publication area, flow_npub)
+constexpr int FLOW_HEAD_MAXG = 62;   // G + 2 items, one lane each
 constexpr long long FLOW_TIMEOUT_TICKS = 5000000;   // 50 ms (s_memrealtime is 100 MHz)
 int flow_trace_count(int T, int nwg);
 
@@ -109,37 +148,6 @@ struct GradArgs {
     // k_reduce_items (nullptr: none)
     double* fpub; long npub;
     double* isent; int nisent;
-};
-
-constexpr int FIN_MAXG = 254;   // theta entries finalize_body stages in LDS (graph kernel: <= 186)
-// k_reduce_items' sentinel protocol (FinArgs::flag) on the fp64 LML path; 0: arrival counter
-#ifndef MFGP_REDUCE_FLAG
-#define MFGP_REDUCE_FLAG 1
-#endif
-struct FinArgs {
-    const double* zpart; int nz;
-    const double* ldiag; int n;
-    const double* gpart; int ng; int gstride;
-    const int* info;
-    int P, D, want_grad;
-    double* out;                      // [lml, grad(G)]
-    // Adam (optional, unconstrained parameters)
-    int adam;
-    double* theta;                    // constrained theta, refreshed after the step
-    double* u; double* m; double* v;
-    const unsigned char* trainable;
-    const int* tie;                   // tie[q]: entries sharing one variable (isotropic lengthscales)
-    int* step;
-    double lr, b1, b2, eps;
-    double* loss_hist;                // loss_hist[step] = -lml (pre-step)
-    int noise_index;                  // theta entry using Shift(1e-6) o Softplus
-    double* items;                    // [2 + G] stage-1 reduction results
-    int G;                            // theta entries (kernel_theta_size)
-    int* cnt;                         // arrival counter (zero on entry): last item workgroup finalizes
-    int flag;                         // 1: items[] hold FLOW_SENTINEL on entry (the Gram launch filled them):
-                                      //    workgroup 0 finalizes once every other item is published
-    int* abortw;                      // flow path: k_chol_flow's abort word -- set: the evaluation timed
-                                      // out (info := MFGP_FLOW_TIMEOUT); workgroup 0 zeroes it for the next
 };
 
 struct PredAArgs {

@@ -16,6 +16,7 @@
 #include "mfgp_device.h"
 #include "mfgp_internal.h"
 #include "mfgp_flow.h"
+#include "mfgp_reduce.h"
 
 namespace mfgp {
 
@@ -1436,32 +1437,11 @@ size_t grad_smem_bytes(int nb, int G, int nil2) {
 // ============================================================ K4: finalize (+Adam)
 
 
-// Stage 2: LML, gradient output and the optional Keras-Adam step; run by the last
-// item workgroup of k_reduce_items to arrive.
-// Adam inputs of theta entry threadIdx.x, loaded at kernel start by the sentinel protocol
-struct FinPre {
-    double u, m, v;
-    int tr;
-};
-__device__ void adam_body(const FinArgs& a, int G, int s, const double* gsh, const int* tsh, const FinPre* pre);
+// Stage 2 (finalize_from, adam_body: mfgp_reduce.h) is run by the last item workgroup of
+// k_reduce_items to arrive, or by workgroup 0 under the sentinel protocol.
 static_assert(FIN_MAXG >= kernel_theta_size(MFGP_MAX_LF, MAXD) && FIN_MAXG >= kernel_theta_size(0, MAXD),
               "finalize_body stages every theta entry in LDS");
 static_assert(FIN_MAXG <= NTHREADS, "one theta entry per finalize thread");
-// gsh = [sum Z^2, sum log L_ii, grad_0 .. grad_{G-1}] in LDS (read after a barrier)
-__device__ void finalize_from(const FinArgs& a, int G, const double* gsh, const int* tsh, int info0, int s,
-                              const FinPre* pre) {
-    const double LOG2PI = 1.8378770664093453;
-    double lml = -0.5 * gsh[0] - (double)a.P * gsh[1] - 0.5 * (double)a.n * (double)a.P * LOG2PI;
-    if (info0 != 0) lml = NAN;
-    if (a.adam && info0 == 0) adam_body(a, G, s, gsh + 2, a.tie ? tsh : nullptr, pre);
-    if (threadIdx.x == 0) a.out[0] = lml;
-    if (a.want_grad)
-        for (int q = threadIdx.x; q < G; q += NTHREADS) a.out[1 + q] = gsh[2 + q];
-    if (!a.adam) return;
-    if (threadIdx.x == 0) a.loss_hist[s] = -lml;
-    __syncthreads();   // every wave has read *a.step
-    if (threadIdx.x == 0 && info0 == 0) *a.step = s + 1;
-}
 __device__ void finalize_body(const FinArgs& a) {
     const int G = a.G ? a.G : theta_size(a.D);
     // every input in ONE round trip into LDS, before the first store (the outputs may alias them
@@ -1474,32 +1454,7 @@ __device__ void finalize_body(const FinArgs& a) {
     const int info0 = a.info[0];
     const int s = a.adam ? *a.step : 0;
     __syncthreads();
-    finalize_from(a, G, gsh, tsh, info0, s, nullptr);
-}
-
-__device__ void adam_body(const FinArgs& a, int G, int s, const double* gsh, const int* tsh, const FinPre* pre) {
-    const double t = (double)(s + 1);
-    const double alpha = a.lr * sqrt(1.0 - pow(a.b2, t)) / (1.0 - pow(a.b1, t));
-    for (int q = threadIdx.x; q < G; q += NTHREADS) {
-        if (pre ? pre->tr : a.trainable[q]) {
-            const double uq = pre ? pre->u : a.u[q];
-            double gc = gsh[q];
-            if (tsh) {   // a variable shared by several theta entries gets the summed gradient
-                gc = 0.0;
-                for (int r = 0; r < G; ++r)
-                    if (tsh[r] == tsh[q]) gc += gsh[r];
-            }
-            const double g = (-gc) / (exp(-uq) + 1.0);   // loss = -lml; TF SoftplusGrad form
-            double mq = pre ? pre->m : a.m[q], vq = pre ? pre->v : a.v[q];
-            mq += (g - mq) * (1.0 - a.b1);
-            vq += (g * g - vq) * (1.0 - a.b2);
-            const double un = uq - (mq * alpha) / (sqrt(vq) + a.eps);
-            a.m[q] = mq;
-            a.v[q] = vq;
-            a.u[q] = un;
-            a.theta[q] = tf_softplus(un) + (q == a.noise_index ? 1e-6 : 0.0);
-        }
-    }
+    finalize_from<NTHREADS>(a, G, gsh, tsh, info0, s, nullptr, threadIdx.x);
 }
 
 // Sentinel protocol, workgroup 0 (FinArgs::flag): the finalize inputs (info, step, Adam state,
@@ -1507,7 +1462,6 @@ __device__ void adam_body(const FinArgs& a, int G, int s, const double* gsh, con
 // until it is no longer FLOW_SENTINEL.  Against store -> drain -> atomic arrival -> sc1 reload
 // by the last workgroup, two memory round trips fewer, and the Adam loads off the tail.  A poll
 // that exceeds REDUCE_TIMEOUT_TICKS (100 MHz) marks the evaluation failed: NaN LML, no Adam step.
-constexpr long long REDUCE_TIMEOUT_TICKS = 5000000;   // 50 ms
 __device__ void reduce_items_wg0(const FinArgs& a) {
     __shared__ double gsh[FIN_MAXG + 2];
     __shared__ int tsh[FIN_MAXG];
@@ -1528,7 +1482,7 @@ __device__ void reduce_items_wg0(const FinArgs& a) {
     if (t == 0) tmo = 0;
     double z = 0.0;
     for (int e = t; e < a.nz; e += NTHREADS) z += a.zpart[e];
-    z = block_sum(z, red);   // (its barriers also order tmo = 0 before the polls)
+    z = block_sum(z, red);   // (reduce_item_thread(a, 0, t), summed; its barriers also order tmo = 0 before the polls)
     if (t >= 1 && t < (int)gridDim.x) {
         const long long t0 = __builtin_amdgcn_s_memrealtime();
         for (;;) {
@@ -1548,7 +1502,7 @@ __device__ void reduce_items_wg0(const FinArgs& a) {
         if (t == 0) const_cast<int*>(a.info)[0] = MFGP_FLOW_TIMEOUT;
     }
     if (a.abortw && t == 0 && aborted) __hip_atomic_store(a.abortw, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    finalize_from(a, G, gsh, tsh, info0, s, &pre);
+    finalize_from<NTHREADS>(a, G, gsh, tsh, info0, s, &pre, threadIdx.x);
 }
 
 // Stage 1 of the step reduction: workgroup `it` sums item `it` of
@@ -1558,30 +1512,7 @@ __global__ __launch_bounds__(NTHREADS) void k_reduce_items(FinArgs a) {
     __shared__ double red[4];
     const int it = blockIdx.x;
     if (a.flag && it == 0) { reduce_items_wg0(a); return; }
-    double s = 0.0;
-    if (it == 0) {
-        for (int e = threadIdx.x; e < a.nz; e += NTHREADS) s += a.zpart[e];
-    } else if (it == 1) {   // 8 loads in flight per thread before the logs
-        for (int e0 = threadIdx.x; e0 < a.n; e0 += 8 * NTHREADS) {
-            double v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = (e0 + u * NTHREADS < a.n) ? a.ldiag[e0 + u * NTHREADS] : 1.0;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += log(v[u]);
-        }
-    } else {
-        const double* src = a.gpart + (long)(it - 2) * a.ng;
-        double s1 = 0.0, s2 = 0.0, s3 = 0.0;
-        int e = threadIdx.x;
-        for (; e + 3 * NTHREADS < a.ng; e += 4 * NTHREADS) {
-            s += src[e];
-            s1 += src[e + NTHREADS];
-            s2 += src[e + 2 * NTHREADS];
-            s3 += src[e + 3 * NTHREADS];
-        }
-        for (; e < a.ng; e += NTHREADS) s += src[e];
-        s = (s + s1) + (s2 + s3);
-    }
+    double s = reduce_item_thread(a, it, threadIdx.x);
     s = block_sum(s, red);
     if (a.flag) {   // sentinel protocol: workgroup 0 polls this item
         if (threadIdx.x == 0) st_coherent(a.items + it, s);

@@ -127,10 +127,11 @@ class Engine:
 
     def mode(self) -> tuple:
         """The handle's execution settings that captured step graphs and workspace sizes depend
-        on: (flow mode, tile size, one-launch small-problem path, k_grad chunk)."""
+        on: (flow mode, tile size, one-launch small-problem path, k_grad chunk, step fusion)."""
         h = self.h
+        fusion = self.lib.mfgp_get_step_fusion(h) if hasattr(self.lib, "mfgp_get_step_fusion") else 0
         return (self.lib.mfgp_get_flow(h), self.lib.mfgp_get_tile(h), self.lib.mfgp_get_tiny(h),
-                self.lib.mfgp_get_grad_chunk(h))
+                self.lib.mfgp_get_grad_chunk(h), fusion)
 
     def tile(self) -> int:
         return self.lib.mfgp_get_tile(self.h)
@@ -261,6 +262,33 @@ class Engine:
                                              ptr(st.u), ptr(st.m), ptr(st.v), ptr(st.trainable), ptr(st.tie),
                                              ptr(st.step), st.lr, st.b1, st.b2, st.eps, ptr(loss_hist), ptr(ws),
                                              ws.numel(), ptr(out), ptr(info)), "mfgp_gpr_adam_step_ex")
+
+    def gpr_adam_steps(self, X, Y, st: "AdamState", loss_hist: torch.Tensor, out: torch.Tensor, info: torch.Tensor,
+                       ws: torch.Tensor = None, nsteps: int = 1):
+        """`nsteps` Adam steps in one call (mfgp_gpr_adam_steps): the same bits as `nsteps` calls of
+        gpr_adam_step; on the fp64 flow path every step's reduction but the last runs in the head of
+        the next flow launch.  float32 inputs take the single-step entry `nsteps` times."""
+        if X.dtype != torch.float64 or not hasattr(self.lib, "mfgp_gpr_adam_steps"):   # (or an older diagnostic build)
+            for _ in range(nsteps):
+                self.gpr_adam_step(X, Y, st, loss_hist, out, info, ws=ws)
+            return
+        n, dp1 = X.shape
+        p = Y.shape[1]
+        d = dp1 - 1
+        nbytes = self.gpr_workspace_bytes(n, p, d, X.dtype)
+        if ws is None:
+            ws = self.workspace("gpr", nbytes)
+        elif ws.numel() < nbytes:
+            raise MFGPError("gpr_adam_steps: private workspace too small")
+        check(self.lib.mfgp_gpr_adam_steps(self.h, n, p, d, ptr(X), dp1, ptr(Y), p, ptr(st.theta), ptr(st.u),
+                                           ptr(st.m), ptr(st.v), ptr(st.trainable), ptr(st.tie), ptr(st.step),
+                                           st.lr, st.b1, st.b2, st.eps, ptr(loss_hist), ptr(ws), ws.numel(),
+                                           ptr(out), ptr(info), int(nsteps)), "mfgp_gpr_adam_steps")
+
+    def set_step_fusion(self, enable: bool):
+        """gpr_adam_steps: defer each step's reduction into the next flow launch (default on; env
+        MFGP_STEP_FUSION=0 turns it off for handles created afterwards)."""
+        self._set_mode(self.lib.mfgp_set_step_fusion, 1 if enable else 0)
 
     def theta_from_u(self, u: torch.Tensor, theta: torch.Tensor, noise_index: int):
         check(self.lib.mfgp_theta_from_u(self.h, ptr(u), ptr(theta), u.numel(), noise_index), "mfgp_theta_from_u")

@@ -427,9 +427,10 @@ def _pool_key(eng, X, Y, lr, max_iters, chunk):
 class AdamSession(_Session):
     """Runs MultiFidelityGPModel Adam iterations on the device.
 
-    State (unconstrained u, moments, step counter, loss history) lives in HBM; each
-    iteration is ONE mfgp_gpr_adam_step call (≈T+6 kernel launches), replayed from
-    hipGraphs of `graph_chunk` iterations on a dedicated stream.  The host only
+    State (unconstrained u, moments, step counter, loss history) lives in HBM; a chunk of
+    iterations is ONE mfgp_gpr_adam_steps call (on the flow path two launches an iteration and one
+    reduction launch a chunk), replayed from hipGraphs of `graph_chunk` iterations on a dedicated
+    stream.  The host only
     syncs when asked (progress prints, finish).  finish() hands the buffers and graphs to the
     session pool, so the next session of the same shape replays them without a capture."""
 
@@ -461,6 +462,12 @@ class AdamSession(_Session):
         # value+grad call): each step leaves it set up for the next (mfgp_set_resident)
         with self.eng.resident():
             self.eng.gpr_adam_step(self.X, self.Y, self.st, self.hist, self.out, self.info, ws=self.ws)
+
+    def _steps(self, n: int):
+        # n steps in one library call: on the flow path each step's reduction but the last runs in
+        # the head of the next flow launch (mfgp_gpr_adam_steps); the same bits as n _step() calls
+        with self.eng.resident():
+            self.eng.gpr_adam_steps(self.X, self.Y, self.st, self.hist, self.out, self.info, ws=self.ws, nsteps=n)
 
     def run(self, n: int):
         if self._core is None:

@@ -67,8 +67,12 @@ class _StepRunner:
     collection that could run in the middle of another session's capture (destroying a graph
     while a stream captures is illegal and aborts the process)."""
 
-    def __init__(self, step, chunk: int, graphs: dict = None):
-        self._step = weakref.WeakMethod(step) if hasattr(step, "__self__") else (lambda f=step: f)
+    def __init__(self, step, chunk: int, graphs: dict = None, steps=None):
+        hold = lambda fn: weakref.WeakMethod(fn) if hasattr(fn, "__self__") else (lambda f=fn: f)
+        self._step = hold(step)
+        # optional steps(n): n steps in ONE call (a session whose library entry runs several);
+        # called once per captured chunk and once for an eager remainder instead of step() n times
+        self._steps = hold(steps) if steps is not None else None
         self.chunk = chunk
         self._owns = graphs is None
         self.graphs = {} if graphs is None else graphs
@@ -78,6 +82,16 @@ class _StepRunner:
         if fn is None:
             raise MFGPError("the training session of this step runner was released")
         fn()
+
+    def steps(self, n: int):
+        if self._steps is None:
+            for _ in range(n):
+                self.step()
+            return
+        fn = self._steps()
+        if fn is None:
+            raise MFGPError("the training session of this step runner was released")
+        fn(n)
 
     def close(self):
         """Release the captured graphs now (retired until exit, see release_retired_graphs)."""
@@ -94,8 +108,7 @@ class _StepRunner:
         if g is None:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                for _ in range(n):
-                    self.step()
+                self.steps(n)
             self.graphs[n] = g
         return g
 
@@ -112,16 +125,14 @@ class _StepRunner:
 
     def run(self, n: int):
         if self.chunk <= 0 or n < 4:
-            for _ in range(n):
-                self.step()
+            self.steps(n)
             return
         full, rem = divmod(n, self.chunk)
         for _ in range(full):
             self._graph(self.chunk).replay()
         if rem:
             if rem < 4:
-                for _ in range(rem):
-                    self.step()
+                self.steps(rem)
             else:
                 self._graph(rem).replay()
 
@@ -148,7 +159,7 @@ class _Session:
         self.eng = eng
         self.max_iters = max(int(max_iters), 1)
         self.stream = new_stream(eng.device) if stream is None and eng is not None else stream
-        self.runner = _StepRunner(self._step, chunk, graphs=graphs)
+        self.runner = _StepRunner(self._step, chunk, graphs=graphs, steps=getattr(self, "_steps", None))
         self.done = 0
         self._warm = warm
 
