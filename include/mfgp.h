@@ -264,6 +264,31 @@ int mfgp_svgp_elbo_grad(mfgp_handle_t h, int n, int m, int l, int p, int d, cons
  * take [L][M][M]. */
 int mfgp_set_svgp_qs_packed(mfgp_handle_t h, int packed);
 
+/* The same ELBO and gradient with the HeteroscedasticGaussian likelihood: every observation has
+ * its own noise variance v[n][c] = noise + Yunc[n][c]^2 (the baseline plus the SQUARED uncertainty,
+ * as the reference's code computes it; its docstring says "+ Y_unc"),
+ *   VE = sum_{n,c} -1/2 log 2 pi - 1/2 log v - 1/2 ((y - f_mu)^2 + f_var) / v.
+ * Yunc [n][ldu] is read for columns 0..p-1 (ldu >= p); a caller holding the reference's combined
+ * targets [Y_obs | Y_unc] of shape [N, 2P] passes Y + P with ldu = ldy.  Yunc == NULL is the
+ * homoscedastic call (mfgp_svgp_elbo / mfgp_svgp_elbo_grad, bit for bit).  gnoise is the gradient
+ * with respect to the baseline.  qs_packed (0 / 1) is the q_sqrt / gq_sqrt layout of THIS call as
+ * mfgp_set_svgp_qs_packed describes it; the handle's setting is not read.  The reverse pass of the
+ * variational expectations is one row-tiled kernel whose LDS holds a row of r and 1/v:
+ * MFGP_ERR_DIM if 2 (p|1) + 4 l > 4000.  Workspaces: mfgp_svgp_workspace_size /
+ * mfgp_svgp_grad_workspace_size.
+ * Replaces: mfgpflow/linear_svgp.py:223-267 (HeteroscedasticGaussian._variational_expectations
+ * under SVGP.elbo and the GradientTape of optimize, linear_svgp.py:181-191). */
+int mfgp_svgp_elbo_het(mfgp_handle_t h, int n, int m, int l, int p, int d, const double* X, int ldx, const double* Y,
+                       int ldy, const double* Yunc, int ldu, const double* Z, int ldz, const double* thetas,
+                       const double* q_mu, const double* q_sqrt, const double* W, double noise, double scale,
+                       double jitter, void* ws, size_t ws_bytes, double* out, double* g_mu, double* g_var, int* info);
+int mfgp_svgp_elbo_grad_het(mfgp_handle_t h, int n, int m, int l, int p, int d, const double* X, int ldx,
+                            const double* Y, int ldy, const double* Yunc, int ldu, const double* Z, int ldz,
+                            const double* thetas, const double* q_mu, const double* q_sqrt, int qs_packed,
+                            const double* W, const double* noise, double scale, double kl_mult, double jitter,
+                            void* ws, size_t ws_bytes, double* out, double* g_mu, double* g_var, double* gZ,
+                            double* gtheta, double* gq_mu, double* gq_sqrt, double* gW, double* gnoise, int* info);
+
 /* One Keras-2.10 (legacy) Adam step on a packed parameter vector (the apply_gradients of
  * the SVGP optimize loops, linear_svgp.py:190 / singlebin_svgp.py:86): u unconstrained,
  * c constrained with transform[q] = 0 identity, 1 Softplus, 2 Shift(1e-6) o Softplus, 3 Sigmoid;

@@ -2,13 +2,15 @@
 
 Public surface mirrors mfgpflow + the GPflow pieces it uses:
     SquaredExponential / RBF, LinearMultiFidelityKernel, MultiFidelityGPModel,
-    LatentMFCoregionalizationSVGP, SingleBinSVGP, PowerSpecs, set_trainable, Parameter.
+    LatentMFCoregionalizationSVGP (with HeteroscedasticGaussian under heterosed=True), SingleBinSVGP,
+    PowerSpecs, set_trainable, Parameter.
 All arithmetic of the hot path runs in libmfgp.so (hand-written HIP for gfx950).
 """
 from .params import Parameter, positive, set_trainable, parameter_dict, multiple_assign  # noqa: F401
 from .kernels import (SquaredExponential, RBF, LinearMultiFidelityKernel,  # noqa: F401
                       LinearCoregionalization, SeparateIndependent)
-from .models import MultiFidelityGPModel, Gaussian, CholeskyError, clear_session_pool  # noqa: F401
+from .models import (MultiFidelityGPModel, Gaussian, HeteroscedasticGaussian, CholeskyError,  # noqa: F401
+                     clear_session_pool)
 from .svgp import LatentMFCoregionalizationSVGP, SingleBinSVGP, initialize_W, initialize_W_pca  # noqa: F401
 from .kernels import GraphMultiFidelityKernel  # noqa: F401
 from .graph import GraphMultiFidelityGPModel  # noqa: F401

@@ -438,6 +438,41 @@ __global__ __launch_bounds__(NTHREADS) void k_svgp_ve(const double* g_mu, const 
     if (threadIdx.x == 0) ve_part[blockIdx.x] = acc;
 }
 
+// The same with the HeteroscedasticGaussian likelihood (linear_svgp.py:243-267): every observation
+// has its own variance v[n][c] = noise + Yunc[n][c]^2 (the baseline plus the SQUARED uncertainty)
+__global__ __launch_bounds__(NTHREADS) void k_svgp_ve_het(const double* g_mu, const double* g_var, const double* W,
+                                                          const double* Y, long ldy, const double* U, long ldu, int n,
+                                                          int p, int L, double noise_h, const double* noise_dev,
+                                                          double* ve_part) {
+    __shared__ double red[4];
+    const double noise = noise_dev ? noise_dev[0] : noise_h;
+    const double LOG2PI = 1.8378770664093453;
+    double acc = 0.0;
+    const long tot = (long)n * p;
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < tot; e += (long)gridDim.x * blockDim.x) {
+        const int r = (int)(e / p), c = (int)(e % p);
+        double fm, fv;
+        if (W) {
+            fm = 0.0;
+            fv = 0.0;
+            for (int l = 0; l < L; ++l) {
+                const double w = W[(long)c * L + l];
+                fm += g_mu[(long)l * n + r] * w;
+                fv += g_var[(long)l * n + r] * (w * w);
+            }
+        } else {
+            fm = g_mu[(long)c * n + r];
+            fv = g_var[(long)c * n + r];
+        }
+        const double u = U[(long)r * ldu + c];
+        const double v = noise + u * u;
+        const double dy = Y[(long)r * ldy + c] - fm;
+        acc += -0.5 * LOG2PI - 0.5 * log(v) - 0.5 * (dy * dy + fv) / v;
+    }
+    acc = block_sum(acc, red);
+    if (threadIdx.x == 0) ve_part[blockIdx.x] = acc;
+}
+
 // posteriors mix_latent_gp (full_cov=False): f_mu = g_mu W^T, f_var = g_var (W o W)^T  (W NULL: identity)
 __global__ void k_svgp_mix(const double* g_mu, const double* g_var, const double* W, int n, int p, int L,
                            double* f_mu, double* f_var) {
@@ -628,8 +663,12 @@ static int svgp_run(hipStream_t s, int n, int m, int L, int p, int d, const doub
         return hipGetLastError() == hipSuccess ? 0 : -3;
     }
     const int nve = 512;
-    hipLaunchKernelGGL(k_svgp_ve, dim3(nve), dim3(NTHREADS), 0, s, g_mu, g_var, W, Y, (long)ldy, n, p, L, noise,
-                       noise_dev, S.ve_part);
+    if (t_side.Yunc)
+        hipLaunchKernelGGL(k_svgp_ve_het, dim3(nve), dim3(NTHREADS), 0, s, g_mu, g_var, W, Y, (long)ldy, t_side.Yunc,
+                           (long)t_side.ldu, n, p, L, noise, noise_dev, S.ve_part);
+    else
+        hipLaunchKernelGGL(k_svgp_ve, dim3(nve), dim3(NTHREADS), 0, s, g_mu, g_var, W, Y, (long)ldy, n, p, L, noise,
+                           noise_dev, S.ve_part);
     hipLaunchKernelGGL(k_svgp_final, dim3(1), dim3(NTHREADS), 0, s, S.ve_part, nve, S.kl_part, L * KL_SLICES, m, L,
                        scale, info, out);
     return hipGetLastError() == hipSuccess ? 0 : -3;

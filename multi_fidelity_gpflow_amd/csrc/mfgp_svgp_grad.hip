@@ -510,6 +510,135 @@ __global__ __launch_bounds__(NTHREADS) void k_gw(const double* r, const double* 
     if (lane == 0) gW[e] = s1 - scale / noise[0] * W[e] * s2;
 }
 
+// ---------------------------------------------------------------- heteroscedastic VE backward
+// HeteroscedasticGaussian (linear_svgp.py:243-267): v[n][c] = s2 + Yunc[n][c]^2 stands where s2 stood,
+// so beta and the g_var term of dE/dW vary with n.  ONE row-tiled kernel replaces k_ve_bwd -> k_ab ->
+// k_gw: a workgroup takes rb rows n, keeps W ([p][L] at an odd row stride) and the rows' g_mu / g_var
+// in LDS, forms f_mu, f_var, v and 1/v per (n, c) in registers and writes
+//   r[n][c]     = scale (y - f_mu) / v
+//   alpha[l][n] = sum_c r[n][c] W[c][l],   beta[l][n] = -scale/2 sum_c W[c][l]^2 / v[n][c]   (zeros up to npad)
+// and one partial per workgroup of dE/ds2 = scale sum (-1/(2v) + ((y - f_mu)^2 + f_var) / (2 v^2)) and of
+//   S1[c][l] = sum_n r[n][c] g_mu[l][n],   S2[c][l] = sum_n g_var[l][n] / v[n][c];
+// k_grad_reduce adds the dE/ds2 partials, k_ve_het_reduce forms dE/dW = S1 - scale W o S2, both in a
+// fixed order (no atomics; every partial is written by its workgroup).  (W == nullptr: identity, L == P.)
+// LDS: 2 rb (p|1) + 2 L (rb + 1) doubles of row state (<= VH_LDS: rb = 16 rows up to p + L ~ 125, halved
+// beyond) + p (L|1) of W (<= VH_LDS, else W is read from global memory): at most 64 KB with red[].
+constexpr int VH_ROWS = 16, VH_LDS = 4000;
+int svgp_ve_het_rows(int p, int l) {
+    int rb = VH_ROWS;
+    while (rb > 0 && (long)rb * 2 * (p | 1) + (long)(rb + 1) * 2 * l > VH_LDS) rb >>= 1;
+    return rb;
+}
+
+__global__ __launch_bounds__(NTHREADS) void k_ve_bwd_het(const double* g_mu, const double* g_var, const double* W,
+                                                         const double* Y, long ldy, const double* U, long ldu, int n,
+                                                         int p, int L, const double* noise, double scale, int npad,
+                                                         int rb, int w_lds, double* r, double* alpha, double* beta,
+                                                         double* gnoise_part, double* gw_part) {
+    extern __shared__ double vh_lds[];
+    __shared__ double red[4];
+    const int ps = p | 1, ls = L | 1, rs1 = rb + 1, t = threadIdx.x;
+    double* rs = vh_lds;            // [rb][ps] r        (zero on the rows past n)
+    double* ivs = rs + rb * ps;     // [rb][ps] 1 / v    (likewise)
+    double* gm = ivs + rb * ps;     // [L][rb + 1] g_mu  (likewise)
+    double* gv = gm + L * rs1;      // [L][rb + 1] g_var (likewise)
+    double* Wl = gv + L * rs1;      // [p][ls] W
+    const int n0 = blockIdx.x * rb;
+    const int nr = min(rb, n - n0);   // live rows (<= 0: a workgroup of the padding)
+    for (int e = t; e < L * rb; e += NTHREADS) {
+        const int l = e / rb, i = e % rb;
+        gm[l * rs1 + i] = (i < nr) ? g_mu[(long)l * n + n0 + i] : 0.0;
+        gv[l * rs1 + i] = (i < nr) ? g_var[(long)l * n + n0 + i] : 0.0;
+    }
+    const double* Wp = W;
+    int wld = L;
+    if (W && w_lds) {
+        for (int e = t; e < p * L; e += NTHREADS) Wl[(e / L) * ls + e % L] = W[e];
+        Wp = Wl;
+        wld = ls;
+    }
+    __syncthreads();
+    const double s2 = noise[0];
+    double gs = 0.0;
+    for (int e = t; e < rb * p; e += NTHREADS) {
+        const int i = e / p, c = e % p;
+        double rv = 0.0, iv = 0.0;
+        if (i < nr) {
+            double fm, fv;
+            if (W) {
+                fm = 0.0;
+                fv = 0.0;
+                for (int l = 0; l < L; ++l) {
+                    const double w = Wp[c * wld + l];
+                    fm += gm[l * rs1 + i] * w;
+                    fv += gv[l * rs1 + i] * (w * w);
+                }
+            } else {
+                fm = gm[c * rs1 + i];
+                fv = gv[c * rs1 + i];
+            }
+            const double u = U[(long)(n0 + i) * ldu + c];
+            iv = 1.0 / (s2 + u * u);
+            const double dy = Y[(long)(n0 + i) * ldy + c] - fm;
+            rv = scale * dy * iv;
+            r[(long)(n0 + i) * p + c] = rv;
+            gs += -0.5 * iv + 0.5 * (dy * dy + fv) * iv * iv;
+        }
+        rs[i * ps + c] = rv;
+        ivs[i * ps + c] = iv;
+    }
+    gs = block_sum(gs, red);   // its barriers also publish rs / ivs
+    if (t == 0) gnoise_part[blockIdx.x] = scale * gs;
+    for (int e = t; e < L * rb; e += NTHREADS) {
+        const int l = e / rb, i = e % rb;
+        double a = 0.0, b = 0.0;
+        if (W) {
+            for (int c = 0; c < p; ++c) {
+                const double w = Wp[c * wld + l];
+                a += rs[i * ps + c] * w;
+                b += (w * w) * ivs[i * ps + c];
+            }
+        } else {
+            a = rs[i * ps + l];
+            b = ivs[i * ps + l];
+        }
+        alpha[(long)l * npad + n0 + i] = a;
+        beta[(long)l * npad + n0 + i] = (i < nr) ? -0.5 * scale * b : 0.0;
+    }
+    if (!W) return;
+    const long pl = (long)p * L;
+    for (int e = t; e < p * L; e += NTHREADS) {
+        const int c = e / L, l = e % L;
+        double s1 = 0.0, sv = 0.0;
+        for (int i = 0; i < rb; ++i) {
+            s1 += rs[i * ps + c] * gm[l * rs1 + i];
+            sv += gv[l * rs1 + i] * ivs[i * ps + c];
+        }
+        gw_part[2 * blockIdx.x * pl + e] = s1;
+        gw_part[(2 * blockIdx.x + 1) * pl + e] = sv;
+    }
+}
+
+// dE/dW[c][l] = sum_b S1_b[c][l] - scale W[c][l] sum_b S2_b[c][l] over the nwg workgroup partials of
+// k_ve_bwd_het: VHR_LANES lanes per entry, lane j the partials b = j mod VHR_LANES, a fixed xor tree
+constexpr int VHR_LANES = 8;
+__global__ void k_ve_het_reduce(const double* gw_part, int nwg, const double* W, int pl, double scale, double* gW) {
+    const long gt = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    const int e = (int)(gt / VHR_LANES), j = (int)(gt % VHR_LANES);
+    double s1 = 0.0, sv = 0.0;
+    if (e < pl)
+        for (int b = j; b < nwg; b += VHR_LANES) {
+            s1 += gw_part[2L * b * pl + e];
+            sv += gw_part[(2L * b + 1) * pl + e];
+        }
+#pragma unroll
+    for (int o = 1; o < VHR_LANES; o <<= 1) {
+        s1 += __shfl_xor(s1, o, 64);
+        sv += __shfl_xor(sv, o, 64);
+    }
+    if (j == 0 && e < pl) gW[e] = s1 - scale * W[e] * sv;
+}
+
 // ---------------------------------------------------------------- kernel derivative sums
 // For pairs (a in P1 = Z rows, b in P2), weight Wt[a][b] (padded row-major):
 //   gth[q] += sum Wt dk/dtheta_q     (q over [vL, lL(D), vD, lD(D), rho])
@@ -865,8 +994,9 @@ __global__ void k_grad_reduce(const double* gth_uu, int nb_uu, const double* gth
 // ---------------------------------------------------------------- driver
 struct SvgpGradLayout {
     double *qm, *alpha, *beta, *A, *B, *gA, *Gb, *H, *P, *Sig, *Kbar, *T1, *gLq, *gqm, *r, *gnp, *gth_uu, *gth_uf,
-        *gth_kff, *gz_uu, *gz_uf;
+        *gth_kff, *gz_uu, *gz_uf, *hnp, *hgw;
     int nbc_uu, nbc_uf, n_at, nb_uu, nb_uf, nnoise;
+    int het_rb, het_nwg;   // k_ve_bwd_het: rows a workgroup, workgroups (hnp / hgw: its dE/ds2 / dE/dW partials)
     size_t bytes;
 };
 
@@ -910,6 +1040,10 @@ static SvgpGradLayout grad_layout(int nb, int n, int m, int L, int p, int d, siz
     g.gth_kff = take((size_t)L * G);
     g.gz_uu = take((size_t)L * g.nb_uu * KG_ROWS * d + 8);
     g.gz_uf = take((size_t)L * g.nb_uf * KG_ROWS * d + 8);
+    g.het_rb = svgp_ve_het_rows(p, L);
+    g.het_nwg = g.het_rb ? npad / g.het_rb : 0;   // npad is a multiple of nb >= 32, rb a power of two <= 16
+    g.hnp = take((size_t)g.het_nwg + 8);
+    g.hgw = take((size_t)g.het_nwg * 2 * p * L + 8);
     g.bytes = off + 256;
     return g;
 }
@@ -968,13 +1102,27 @@ static int svgp_grad_run(hipStream_t s, int n, int m, int L, int p, int d, const
     const int Tm = mpad / NB, Tn = npad / NB;
     const long mm = (long)mpad * mpad, mn = (long)mpad * npad;
     const int G = theta_size(d);
-    // 1. VE backward
-    hipLaunchKernelGGL(k_ve_bwd, dim3(g.nnoise), dim3(NTHREADS), 0, s, g_mu, g_var, W, Y, (long)ldy, n, p, L,
-                       noise_dev, scale, npad, g.r, g.alpha, g.beta, g.gnp);
-    hipLaunchKernelGGL(k_ab, dim3(cdv(npad, 256), 1, L), dim3(256), 0, s, g.r, W, n, p, L, noise_dev, scale, npad,
-                       g.alpha, g.beta);
-    if (W) hipLaunchKernelGGL(k_gw, dim3(cdv(p * L, NTHREADS / 64)), dim3(NTHREADS), 0, s, g.r, g_mu, g_var, W, n, p, L,
-                              noise_dev, scale, gW);
+    // 1. VE backward (heteroscedastic: the fused row-tiled kernel and its dE/dW reduction)
+    const double* Yunc = svgp_side().Yunc;
+    if (Yunc) {
+        if (g.het_rb == 0) return -4;
+        const int ps = p | 1, ls = L | 1;
+        const int w_lds = (W && (long)p * ls <= VH_LDS) ? 1 : 0;
+        const size_t smem = sizeof(double) * ((size_t)g.het_rb * 2 * ps + (size_t)(g.het_rb + 1) * 2 * L +
+                                              (w_lds ? (size_t)p * ls : 0));
+        hipLaunchKernelGGL(k_ve_bwd_het, dim3(g.het_nwg), dim3(NTHREADS), smem, s, g_mu, g_var, W, Y, (long)ldy, Yunc,
+                           (long)svgp_side().ldu, n, p, L, noise_dev, scale, npad, g.het_rb, w_lds, g.r, g.alpha,
+                           g.beta, g.hnp, g.hgw);
+        if (W) hipLaunchKernelGGL(k_ve_het_reduce, dim3(cdv(p * L * VHR_LANES, 256)), dim3(256), 0, s, g.hgw, g.het_nwg,
+                                  W, p * L, scale, gW);
+    } else {
+        hipLaunchKernelGGL(k_ve_bwd, dim3(g.nnoise), dim3(NTHREADS), 0, s, g_mu, g_var, W, Y, (long)ldy, n, p, L,
+                           noise_dev, scale, npad, g.r, g.alpha, g.beta, g.gnp);
+        hipLaunchKernelGGL(k_ab, dim3(cdv(npad, 256), 1, L), dim3(256), 0, s, g.r, W, n, p, L, noise_dev, scale, npad,
+                           g.alpha, g.beta);
+        if (W) hipLaunchKernelGGL(k_gw, dim3(cdv(p * L, NTHREADS / 64)), dim3(NTHREADS), 0, s, g.r, g_mu, g_var, W, n, p,
+                                  L, noise_dev, scale, gW);
+    }
     hipLaunchKernelGGL(k_qmu_pad, dim3(cdv(mpad, 256), 1, L), dim3(256), 0, s, q_mu, m, L, mpad, g.qm);
     // Two branches after gA (ONE fork, one join): the side takes dE/dm, dE/dLq, Kbar -> the (Z, X)
     // derivative sums and the K_diag term; the caller's stream Gb -> Sigma_bar -> the (Z, Z) sums.
@@ -1085,8 +1233,8 @@ static int svgp_grad_run(hipStream_t s, int n, int m, int L, int p, int d, const
     svgp_join(s);
     const int tot = L * G + m * (d + 1) + 1;
     hipLaunchKernelGGL(k_grad_reduce, dim3(cdv(tot * GR_LANES, 256)), dim3(256), 0, s, g.gth_uu, g.nb_uu, g.gth_uf, g.nb_uf,
-                       g.gth_kff, g.gz_uu, g.gz_uf, g.n_at, g.nbc_uu, g.nbc_uf, L, G, d, m, g.gnp, g.nnoise, gtheta,
-                       gZ, gnoise);
+                       g.gth_kff, g.gz_uu, g.gz_uf, g.n_at, g.nbc_uu, g.nbc_uf, L, G, d, m, Yunc ? g.hnp : g.gnp,
+                       Yunc ? g.het_nwg : g.nnoise, gtheta, gZ, gnoise);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

@@ -395,7 +395,17 @@ class Engine:
             return Linv[0], ld[0], info
         return Linv, ld, info
 
-    def svgp_elbo(self, X, Y, Z, thetas, q_mu, q_sqrt, W, noise, scale, jitter=1e-6):
+    @staticmethod
+    def _check_yunc(Yunc, Y, n, p):
+        """The heteroscedastic entry points' Yunc: fp64 [n, >= p] on Y's device, unit inner stride."""
+        assert Yunc.dtype == torch.float64, "Yunc must be float64"
+        assert Yunc.device == Y.device, "Yunc must live on Y's device"
+        assert Yunc.dim() == 2 and Yunc.shape[0] == n and Yunc.shape[1] >= p, f"Yunc must be [{n}, >= {p}]"
+        assert Yunc.stride(1) == 1 and Yunc.stride(0) >= p, "Yunc needs a unit inner stride"
+
+    def svgp_elbo(self, X, Y, Z, thetas, q_mu, q_sqrt, W, noise, scale, jitter=1e-6, Yunc=None):
+        """SVGP ELBO value; with Yunc [n, >= p] the HeteroscedasticGaussian one (noise + Yunc**2 per
+        observation, mfgp_svgp_elbo_het), where Y may be a row-strided view (the [N, 2P] targets' halves)."""
         n, dp1 = X.shape
         d = dp1 - 1
         p = Y.shape[1]
@@ -407,6 +417,15 @@ class Engine:
         g_mu = torch.empty((L, n), dtype=torch.float64, device=self.device)
         g_var = torch.empty((L, n), dtype=torch.float64, device=self.device)
         info = torch.empty((L,), dtype=torch.int32, device=self.device)
+        if Yunc is not None:
+            self._check_yunc(Yunc, Y, n, p)
+            assert Y.stride(1) == 1, "Y needs a unit inner stride"
+            check(self.lib.mfgp_svgp_elbo_het(self.h, n, m, L, p, d, ptr(X), dp1, ptr(Y), Y.stride(0), ptr(Yunc),
+                                              Yunc.stride(0), ptr(Z), Z.shape[1], ptr(thetas), ptr(q_mu),
+                                              ptr(q_sqrt), ptr(W), float(noise), float(scale), float(jitter),
+                                              ptr(ws), ws.numel(), ptr(out), ptr(g_mu), ptr(g_var), ptr(info)),
+                  "mfgp_svgp_elbo_het")
+            return out, g_mu, g_var, info
         check(self.lib.mfgp_svgp_elbo(self.h, n, m, L, p, d, ptr(X), dp1, ptr(Y), p, ptr(Z), Z.shape[1],
                                       ptr(thetas), ptr(q_mu), ptr(q_sqrt), ptr(W), float(noise), float(scale),
                                       float(jitter), ptr(ws), ws.numel(), ptr(out), ptr(g_mu), ptr(g_var),
@@ -417,10 +436,12 @@ class Engine:
         return self._size(self.lib.mfgp_svgp_grad_workspace_size, n, m, L, p, d)
 
     def svgp_elbo_grad(self, X, Y, Z, thetas, q_mu, q_sqrt, W, noise, scale, kl_mult, jitter, out, g_mu, g_var,
-                       gZ, gtheta, gq_mu, gq_sqrt, gW, gnoise, info, ws=None, qs_packed=False):
+                       gZ, gtheta, gq_mu, gq_sqrt, gW, gnoise, info, ws=None, qs_packed=False, Yunc=None):
         """Gradient of VE*scale - kl_mult*KL w.r.t. the constrained SVGP parameters (all device
         tensors, written in place; noise is a device scalar).  qs_packed: q_sqrt and gq_sqrt are
-        packed lower triangles [L, M(M+1)/2] (mfgp_set_svgp_qs_packed), else [L, M, M]."""
+        packed lower triangles [L, M(M+1)/2] (mfgp_set_svgp_qs_packed), else [L, M, M].  Yunc
+        [n, >= p]: the HeteroscedasticGaussian likelihood (mfgp_svgp_elbo_grad_het, which takes
+        qs_packed as an argument, not from the handle)."""
         n, dp1 = X.shape
         d = dp1 - 1
         p = Y.shape[1]
@@ -432,6 +453,17 @@ class Engine:
         elif ws.numel() < nbytes:
             raise MFGPError("svgp_elbo_grad: private workspace too small")
         h = self.h
+        if Yunc is not None:
+            self._check_yunc(Yunc, Y, n, p)
+            assert Y.stride(1) == 1, "Y needs a unit inner stride"
+            check(self.lib.mfgp_svgp_elbo_grad_het(h, n, m, L, p, d, ptr(X), dp1, ptr(Y), Y.stride(0), ptr(Yunc),
+                                                   Yunc.stride(0), ptr(Z), dp1, ptr(thetas), ptr(q_mu), ptr(q_sqrt),
+                                                   1 if qs_packed else 0, ptr(W), ptr(noise), float(scale),
+                                                   float(kl_mult), float(jitter), ptr(ws), ws.numel(), ptr(out),
+                                                   ptr(g_mu), ptr(g_var), ptr(gZ), ptr(gtheta), ptr(gq_mu),
+                                                   ptr(gq_sqrt), ptr(gW), ptr(gnoise), ptr(info)),
+                  "mfgp_svgp_elbo_grad_het")
+            return
         check(self.lib.mfgp_set_svgp_qs_packed(h, 1 if qs_packed else 0), "mfgp_set_svgp_qs_packed")
         try:
             check(self.lib.mfgp_svgp_elbo_grad(h, n, m, L, p, d, ptr(X), dp1, ptr(Y), Y.stride(0), ptr(Z), dp1,

@@ -44,6 +44,19 @@ class Gaussian(Module):
         self.variance = Parameter(variance, transform=positive(lower=variance_lower_bound))
 
 
+class HeteroscedasticGaussian(Gaussian):
+    """mfgpflow/linear_svgp.py:223-267: Gaussian noise with a per-observation uncertainty.  The
+    targets are the combined array [Y_obs | Y_unc] of shape [N, 2P]; observation (n, c) has the
+    variance ``variance + Y_unc[n, c]**2`` (the code squares the uncertainty; its docstring does
+    not).  ``variance`` is the trainable baseline of shape (1,) (the reference passes
+    np.array([1.0])), wrapped in gpflow.utilities.positive() with no lower bound: a plain Softplus,
+    not the Shift(1e-6) of ``Gaussian``.  predict_y adds the baseline only (GPflow's
+    Gaussian._predict_mean_and_var reads self.variance)."""
+
+    def __init__(self, variance=1.0):
+        self.variance = Parameter(np.reshape(np.asarray(variance, dtype=np.float64), (1,)), transform=positive())
+
+
 class _ThetaMap:
     """Maps the model's Parameters onto the device theta vector
     [vL, lL(d), vD, lD(d), rho0, noise] of include/mfgp.h."""

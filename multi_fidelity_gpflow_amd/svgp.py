@@ -2,7 +2,9 @@
 
 * ``LatentMFCoregionalizationSVGP`` — mfgpflow/linear_svgp.py:64-221: L latent
   LinearMultiFidelityKernels mixed by W (LinearCoregionalization), KMeans
-  inducing points, whitened q(u).
+  inducing points, whitened q(u).  ``heterosed=True`` (linear_svgp.py:133-136, :223-267): the
+  HeteroscedasticGaussian likelihood over targets [Y_obs | Y_unc] of shape [N, 2P], per-observation
+  variance = baseline + Y_unc**2 (mfgp_svgp_elbo_het / mfgp_svgp_elbo_grad_het).
 * ``SingleBinSVGP`` — mfgpflow/singlebin_svgp.py:13-135: one LinearMultiFidelityKernel
   per output bin (SeparateIndependent), q_sqrt = 0.1 I.
 
@@ -22,7 +24,7 @@ import torch
 
 from .engine import Engine, theta_size, to_dev
 from .kernels import LinearCoregionalization, LinearMultiFidelityKernel, SeparateIndependent
-from .models import CholeskyError, Gaussian
+from .models import CholeskyError, Gaussian, HeteroscedasticGaussian
 from .params import (Module, Parameter, Softplus, as_result, gather_entries, multiple_assign, parameter_dict,
                      scatter_entries, tie_entries)
 from .session import _PackedAdam, _Session, check_outcome, span_from_tie
@@ -90,13 +92,38 @@ class _SVGPBase(Module):
         W = None if W is None else to_dev(W, eng.device)
         return eng, Z, thetas, q_mu, q_sqrt, W
 
+    def _noise(self) -> float:
+        """The likelihood's (baseline) variance as a python float: shape () or (1,)."""
+        return float(np.reshape(self.likelihood.variance.numpy(), -1)[0])
+
+    def _heteroscedastic(self) -> bool:
+        return isinstance(self.likelihood, HeteroscedasticGaussian)
+
+    def _check_targets(self, Y):
+        """HeteroscedasticGaussian: the targets are [Y_obs | Y_unc], [N, 2P] (linear_svgp.py:246-249).
+        Host-side, before any device work."""
+        if self._heteroscedastic():
+            shape, P = tuple(np.shape(Y)), self.num_outputs
+            if len(shape) != 2 or shape[1] != 2 * P:
+                raise ValueError(f"heteroscedastic targets must have shape [N, {2 * P}] = [N, 2 * num_outputs] "
+                                 f"(the observations, then their uncertainties); got {list(shape)}")
+
+    def _split_targets(self, Yd):
+        """(Y_obs, Y_unc or None): views of the one device tensor, no copy."""
+        if not self._heteroscedastic():
+            return Yd, None
+        P = self.num_outputs
+        return Yd[:, :P], Yd[:, P:]
+
     def _elbo_parts(self, data):
         X, Y = data
+        self._check_targets(Y)
         eng, Z, thetas, q_mu, q_sqrt, W = self._dev_state()
         Xd, Yd = to_dev(X, eng.device), to_dev(Y, eng.device)
+        Yd, Yunc = self._split_targets(Yd)
         scale = (self.num_data / Xd.shape[0]) if self.num_data else 1.0
-        out, g_mu, g_var, info = eng.svgp_elbo(Xd, Yd, Z, thetas, q_mu, q_sqrt, W,
-                                               float(self.likelihood.variance.numpy()), scale, DEFAULT_JITTER)
+        out, g_mu, g_var, info = eng.svgp_elbo(Xd, Yd, Z, thetas, q_mu, q_sqrt, W, self._noise(), scale,
+                                               DEFAULT_JITTER, Yunc=Yunc)
         if int(info.max().item()) != 0:
             raise CholeskyError("elbo: Cholesky of K_uu was not successful")
         return out
@@ -135,13 +162,14 @@ class _SVGPBase(Module):
         return as_result(f_mu), as_result(f_var)
 
     def predict_y(self, Xnew, full_cov=False, full_output_cov=False):
-        """GPflow GPModel.predict_y: predict_f plus the Gaussian noise variance."""
+        """GPflow GPModel.predict_y: predict_f plus the Gaussian noise variance (the baseline alone
+        for HeteroscedasticGaussian: Gaussian._predict_mean_and_var reads self.variance)."""
         if full_cov or full_output_cov:
             # GPflow 2.9 GPModel.predict_y (gpflow issue 1461): only the marginal form is supported
             raise NotImplementedError("The predict_y method currently supports only the argument values "
                                       "full_cov=False and full_output_cov=False")
         mean, var = self.predict_f(Xnew)
-        return mean, as_result(var + float(self.likelihood.variance.numpy()))
+        return mean, as_result(var + self._noise())
 
     def elbo_and_grad(self, data, kl_multiplier=1.0):
         """(ELBO, dict of d(VE*scale - kl_multiplier*KL)/d(constrained parameter)) on the device:
@@ -225,10 +253,11 @@ class _SVGPTrainer(_Session):
         """max_iters: the iterations this trainer runs; decay_steps (default max_iters): the
         CosineDecay length, whose schedule starts at step 0 for this trainer's first iteration."""
         self.model = model
+        X, Y = data
+        model._check_targets(Y)
         eng = Engine.get()
         super().__init__(eng, max_iters, graph_chunk if graph else 0)
         dev = eng.device
-        X, Y = data
         Xh = np.ascontiguousarray(np.asarray(X.cpu() if isinstance(X, torch.Tensor) else X, dtype=np.float64))
         Yh = np.ascontiguousarray(np.asarray(Y.cpu() if isinstance(Y, torch.Tensor) else Y, dtype=np.float64))
         if Yh.ndim == 1:
@@ -241,7 +270,8 @@ class _SVGPTrainer(_Session):
         kernels = model.kernel.kernels
         L = len(kernels)
         G = theta_size(d)
-        p = Yh.shape[1]
+        # heteroscedastic targets are [Y_obs | Y_unc]: the outputs are num_outputs, not Y's columns
+        p = model.num_outputs if model._heteroscedastic() else Yh.shape[1]
         self.L, self.G, self.p = L, G, p
         Wp = model.kernel.W if isinstance(model.kernel, LinearCoregionalization) else None
         # ---- packed layout: (name, shape, c, u, trainable, transform, span)
@@ -294,7 +324,9 @@ class _SVGPTrainer(_Session):
         f64 = dict(dtype=torch.float64, device=dev)
         with self._ctx():
             self.X = torch.tensor(Xh, **f64)
-            self.Y = torch.tensor(Yh, **f64)
+            # one tensor for the life of the graphs; heteroscedastic: Y / Yunc are its two halves
+            # (views: captured replays read stable addresses, Yunc = Y + P with Y's row stride)
+            self.Y, self.Yunc = model._split_targets(torch.tensor(Yh, **f64))
             decay = self.max_iters if decay_steps is None else int(decay_steps)
             self.opt = _PackedAdam(dev, np.concatenate(us), np.concatenate(cs), np.concatenate(trs),
                                    np.concatenate(tfs), np.concatenate(sps),
@@ -340,7 +372,7 @@ class _SVGPTrainer(_Session):
                                 self.view(c, "q_sqrt"), W, self.view(c, "noise"), self.scale, self.klm,
                                 DEFAULT_JITTER, self.out, self.g_mu, self.g_var, self.view(g, "Z"),
                                 self.view(g, "theta"), self.view(g, "q_mu"), self.view(g, "q_sqrt"), gW,
-                                self.view(g, "noise"), self.info, ws=self.ws, qs_packed=True)
+                                self.view(g, "noise"), self.info, ws=self.ws, qs_packed=True, Yunc=self.Yunc)
 
     def _step(self):
         self._grad()
@@ -400,8 +432,13 @@ class LatentMFCoregionalizationSVGP(_SVGPBase):
 
     def __init__(self, X, Y, kernel_L, kernel_delta, num_latents, num_inducing, num_outputs, use_rho=True,
                  heterosed=False, loss_type='gaussian', w_type='diagonal', window_fraction=0.4, scale=0.2):
-        if heterosed:
-            raise NotImplementedError("heteroscedastic likelihoods are out of scope (SURVEY §2)")
+        # heterosed (linear_svgp.py:133-139): HeteroscedasticGaussian over targets [Y_obs | Y_unc] of
+        # shape [N, 2 num_outputs]; the Poisson variant is a stub in the reference itself
+        if heterosed and loss_type == 'poisson':
+            raise NotImplementedError("heterosed=True with loss_type='poisson' is not supported: the reference marks "
+                                      "HeteroscedasticPoisson 'NOT FULLY IMPLEMENTED' (linear_svgp.py:288)")
+        if heterosed and loss_type != 'gaussian':
+            raise ValueError(f"Unknown loss_type: {loss_type}. heterosed=True supports 'gaussian'.")
         self.num_outputs = num_outputs
         self.num_latents = num_latents
         self.loss_type = loss_type
@@ -419,7 +456,8 @@ class LatentMFCoregionalizationSVGP(_SVGPBase):
         Z = kmeans_inducing(np.asarray(X), num_inducing, 42)
         M = Z.shape[0]
         self._setup(Z, np.zeros((M, num_latents)), np.tile(np.eye(M)[None], (num_latents, 1, 1)),
-                    Gaussian(variance=1.0), np.asarray(X).shape[0])
+                    HeteroscedasticGaussian(variance=np.array([1.0])) if heterosed else Gaussian(variance=1.0),
+                    np.asarray(X).shape[0])
         self.kl_history = []
 
     def _W(self):
