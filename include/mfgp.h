@@ -289,6 +289,34 @@ int mfgp_svgp_elbo_grad_het(mfgp_handle_t h, int n, int m, int l, int p, int d, 
                             void* ws, size_t ws_bytes, double* out, double* g_mu, double* g_var, double* gZ,
                             double* gtheta, double* gq_mu, double* gq_sqrt, double* gW, double* gnoise, int* info);
 
+/* The same ELBO and gradient with the MaskedGaussian likelihood: a NaN in Y is a missing observation,
+ * and every output has its own noise variance.  With obs[n][c] = !isnan(Y[n][c]) and
+ * s2[c] = noise[pn == 1 ? 0 : c],
+ *   VE = sum_{obs} -1/2 log 2 pi - 1/2 log s2[c] - 1/2 ((y - f_mu)^2 + f_var) / s2[c];
+ * a missing entry adds exactly 0 to the value and to every gradient, and ELBO = VE scale - kl_mult KL
+ * with the caller's scale (num_data / n: n counts rows, not observed entries).  noise is a DEVICE
+ * vector of pn entries, pn = 1 (one shared variance) or pn = p (one per output); any other pn is
+ * MFGP_ERR_ARG.  gnoise [pn] is the gradient with respect to noise; an output with no observed entry
+ * gets exactly 0.  Y [n][ldy], ldy >= p.  qs_packed (0 / 1) is the q_sqrt / gq_sqrt layout of THIS
+ * call as mfgp_set_svgp_qs_packed describes it; the handle's setting is not read.  The reverse pass of
+ * the variational expectations is one row-tiled kernel whose LDS holds a row of r, obs / s2 and the
+ * noise-gradient terms: MFGP_ERR_DIM if 3 (p|1) + 4 l > 4000.  No atomics: gradients are bitwise
+ * reproducible and do not depend on the workspace contents.  Workspaces: mfgp_svgp_workspace_size /
+ * mfgp_svgp_grad_workspace_size.
+ * Replaces: notebooks/demo: missing output.ipynb, cell 2 (MaskedGaussian._variational_expectations
+ * under SVGP.elbo, and the GradientTape of that cell's optimize). */
+int mfgp_svgp_elbo_masked(mfgp_handle_t h, int n, int m, int l, int p, int d, const double* X, int ldx,
+                          const double* Y, int ldy, const double* Z, int ldz, const double* thetas, const double* q_mu,
+                          const double* q_sqrt, const double* W, const double* noise, int pn, double scale,
+                          double jitter, void* ws, size_t ws_bytes, double* out, double* g_mu, double* g_var,
+                          int* info);
+int mfgp_svgp_elbo_grad_masked(mfgp_handle_t h, int n, int m, int l, int p, int d, const double* X, int ldx,
+                               const double* Y, int ldy, const double* Z, int ldz, const double* thetas,
+                               const double* q_mu, const double* q_sqrt, int qs_packed, const double* W,
+                               const double* noise, int pn, double scale, double kl_mult, double jitter, void* ws,
+                               size_t ws_bytes, double* out, double* g_mu, double* g_var, double* gZ, double* gtheta,
+                               double* gq_mu, double* gq_sqrt, double* gW, double* gnoise, int* info);
+
 /* One Keras-2.10 (legacy) Adam step on a packed parameter vector (the apply_gradients of
  * the SVGP optimize loops, linear_svgp.py:190 / singlebin_svgp.py:86): u unconstrained,
  * c constrained with transform[q] = 0 identity, 1 Softplus, 2 Shift(1e-6) o Softplus, 3 Sigmoid;

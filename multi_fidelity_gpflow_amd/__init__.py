@@ -3,14 +3,15 @@
 Public surface mirrors mfgpflow + the GPflow pieces it uses:
     SquaredExponential / RBF, LinearMultiFidelityKernel, MultiFidelityGPModel,
     LatentMFCoregionalizationSVGP (with HeteroscedasticGaussian under heterosed=True), SingleBinSVGP,
+    MaskedGaussian (missing_outputs=True on either SVGP emulator: NaN targets are missing observations),
     PowerSpecs, set_trainable, Parameter.
 All arithmetic of the hot path runs in libmfgp.so (hand-written HIP for gfx950).
 """
 from .params import Parameter, positive, set_trainable, parameter_dict, multiple_assign  # noqa: F401
 from .kernels import (SquaredExponential, RBF, LinearMultiFidelityKernel,  # noqa: F401
                       LinearCoregionalization, SeparateIndependent)
-from .models import (MultiFidelityGPModel, Gaussian, HeteroscedasticGaussian, CholeskyError,  # noqa: F401
-                     clear_session_pool)
+from .models import (MultiFidelityGPModel, Gaussian, HeteroscedasticGaussian, MaskedGaussian,  # noqa: F401
+                     CholeskyError, clear_session_pool)
 from .svgp import LatentMFCoregionalizationSVGP, SingleBinSVGP, initialize_W, initialize_W_pca  # noqa: F401
 from .kernels import GraphMultiFidelityKernel  # noqa: F401
 from .graph import GraphMultiFidelityGPModel  # noqa: F401

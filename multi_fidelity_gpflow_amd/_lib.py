@@ -74,6 +74,10 @@ SIGNATURES = {
                            _sz, _p, _p, _p, _p],
     "mfgp_svgp_elbo_grad_het": [_p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _i, _p, _p, _d,
                                 _d, _d, _p, _sz, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "mfgp_svgp_elbo_masked": [_p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _i, _d, _d, _p, _sz,
+                              _p, _p, _p, _p],
+    "mfgp_svgp_elbo_grad_masked": [_p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _i, _p, _p, _i, _d, _d,
+                                   _d, _p, _sz, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "mfgp_adam_packed": [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _d, _d, _d, _p, _d, _p, _p],
     "mfgp_adam_packed_ex": [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _d, _d, _d, _p, _d, _p, _p, _p, _i],
     "mfgp_gmf_gram": [_p, _i, _i, _i, _i, _p, _i, _p, _i, _p, _d, _p, _i],

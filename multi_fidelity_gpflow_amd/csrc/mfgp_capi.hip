@@ -1333,6 +1333,53 @@ int mfgp_svgp_elbo_grad_het(mfgp_handle_t h, int n, int m, int l, int p, int d, 
                           gnoise, info);
 }
 
+int mfgp_svgp_elbo_masked(mfgp_handle_t h, int n, int m, int l, int p, int d, const double* X, int ldx,
+                          const double* Y, int ldy, const double* Z, int ldz, const double* thetas, const double* q_mu,
+                          const double* q_sqrt, const double* W, const double* noise, int pn, double scale,
+                          double jitter, void* ws, size_t ws_bytes, double* out, double* g_mu, double* g_var,
+                          int* info) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (n < 1 || m < 1 || l < 1 || p < 1 || !X || !Y || !Z || !thetas || !q_mu || !q_sqrt || !noise || !ws || !out ||
+        !info)
+        return MFGP_ERR_ARG;
+    if (!W && l != p) return MFGP_ERR_ARG;
+    if (pn != 1 && pn != p) return MFGP_ERR_ARG;
+    if (ldy < p) return MFGP_ERR_ARG;
+    SvgpSide sd{h->side, h->ev_fork, h->ev_join};
+    sd.mnoise = noise;
+    sd.pn = pn;
+    svgp_set_side(sd);
+    return svgp_elbo_impl(h->stream, h->nb, n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, W, 0.0, scale,
+                          jitter, ws, ws_bytes, out, g_mu, g_var, info, noise);
+}
+
+int mfgp_svgp_elbo_grad_masked(mfgp_handle_t h, int n, int m, int l, int p, int d, const double* X, int ldx,
+                               const double* Y, int ldy, const double* Z, int ldz, const double* thetas,
+                               const double* q_mu, const double* q_sqrt, int qs_packed, const double* W,
+                               const double* noise, int pn, double scale, double kl_mult, double jitter, void* ws,
+                               size_t ws_bytes, double* out, double* g_mu, double* g_var, double* gZ, double* gtheta,
+                               double* gq_mu, double* gq_sqrt, double* gW, double* gnoise, int* info) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (n < 1 || m < 1 || l < 1 || p < 1 || !X || !Y || !Z || !thetas || !q_mu || !q_sqrt || !noise || !ws ||
+        !out || !g_mu || !g_var || !gZ || !gtheta || !gq_mu || !gq_sqrt || !gnoise || !info)
+        return MFGP_ERR_ARG;
+    if (qs_packed != 0 && qs_packed != 1) return MFGP_ERR_ARG;
+    if (pn != 1 && pn != p) return MFGP_ERR_ARG;
+    if (W == nullptr && l != p) return MFGP_ERR_ARG;
+    if (W != nullptr && gW == nullptr) return MFGP_ERR_ARG;
+    if (ldx < d + 1 || ldz < d + 1 || ldy < p) return MFGP_ERR_ARG;
+    if (svgp_ve_masked_rows(p, l) == 0) return MFGP_ERR_DIM;
+    SvgpSide sd{h->side, h->ev_fork, h->ev_join, qs_packed};
+    sd.mnoise = noise;
+    sd.pn = pn;
+    svgp_set_side(sd);
+    return svgp_grad_impl(h->stream, h->nb, n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, W, noise, 0.0,
+                          scale, kl_mult, jitter, ws, ws_bytes, out, g_mu, g_var, gZ, gtheta, gq_mu, gq_sqrt, gW,
+                          gnoise, info);
+}
+
 int mfgp_set_svgp_qs_packed(mfgp_handle_t h, int packed) {
     CHECK_H(h);
     if (packed != 0 && packed != 1) return MFGP_ERR_ARG;

@@ -202,16 +202,21 @@ void launch_bgemm(int nb, hipStream_t st, int ta, int tb, const BgemmArgs& a, in
 // its side stream and fork / join events; qs_packed: q_sqrt / gq_sqrt of the gradient entry as packed
 // lower triangles [L][M(M+1)/2] (mfgp_set_svgp_qs_packed, or mfgp_svgp_elbo_grad_het's argument);
 // Yunc / ldu: the per-observation uncertainties [n][ldu] of the heteroscedastic entry points
-// (nullptr: the homoscedastic Gaussian likelihood, today's kernels and launch sequence)
+// (nullptr: the homoscedastic Gaussian likelihood, today's kernels and launch sequence);
+// mnoise / pn: the device noise vector of the MaskedGaussian entry points, pn = 1 or p entries
+// (pn == 0: not masked; NaN targets then propagate as they always did)
 struct SvgpSide {
     hipStream_t side; hipEvent_t fork, join; int qs_packed = 0;
     const double* Yunc = nullptr; int ldu = 0;
+    const double* mnoise = nullptr; int pn = 0;
 };
 void svgp_set_side(const SvgpSide& sd);
 const SvgpSide& svgp_side();
 // rows a workgroup of the heteroscedastic VE reverse kernel takes (k_ve_bwd_het) for p outputs and
 // l latents; 0: the row state of one row does not fit its LDS budget (MFGP_ERR_DIM)
 int svgp_ve_het_rows(int p, int l);
+// the same for the masked VE reverse kernel (k_ve_bwd_masked), whose row state has a third [rb][p|1] tile
+int svgp_ve_masked_rows(int p, int l);
 
 // fork the side stream off s (nothing without a side stream); returns the stream to launch on
 hipStream_t svgp_fork(hipStream_t s);

@@ -473,6 +473,41 @@ __global__ __launch_bounds__(NTHREADS) void k_svgp_ve_het(const double* g_mu, co
     if (threadIdx.x == 0) ve_part[blockIdx.x] = acc;
 }
 
+// The same with the MaskedGaussian likelihood (notebooks/demo: missing output.ipynb, cell 2): a NaN
+// target is a missing observation and adds nothing; output c has the variance noise[pn == 1 ? 0 : c].
+// The entry is left out by a select on y == y (no fast-math in this build), not by a product with 0.
+__global__ __launch_bounds__(NTHREADS) void k_svgp_ve_masked(const double* g_mu, const double* g_var, const double* W,
+                                                             const double* Y, long ldy, int n, int p, int L,
+                                                             const double* noise, int pn, double* ve_part) {
+    __shared__ double red[4];
+    const double LOG2PI = 1.8378770664093453;
+    double acc = 0.0;
+    const long tot = (long)n * p;
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < tot; e += (long)gridDim.x * blockDim.x) {
+        const int r = (int)(e / p), c = (int)(e % p);
+        const double y = Y[(long)r * ldy + c];
+        if (!(y == y)) continue;
+        double fm, fv;
+        if (W) {
+            fm = 0.0;
+            fv = 0.0;
+            for (int l = 0; l < L; ++l) {
+                const double w = W[(long)c * L + l];
+                fm += g_mu[(long)l * n + r] * w;
+                fv += g_var[(long)l * n + r] * (w * w);
+            }
+        } else {
+            fm = g_mu[(long)c * n + r];
+            fv = g_var[(long)c * n + r];
+        }
+        const double v = noise[pn == 1 ? 0 : c];
+        const double dy = y - fm;
+        acc += -0.5 * LOG2PI - 0.5 * log(v) - 0.5 * (dy * dy + fv) / v;
+    }
+    acc = block_sum(acc, red);
+    if (threadIdx.x == 0) ve_part[blockIdx.x] = acc;
+}
+
 // posteriors mix_latent_gp (full_cov=False): f_mu = g_mu W^T, f_var = g_var (W o W)^T  (W NULL: identity)
 __global__ void k_svgp_mix(const double* g_mu, const double* g_var, const double* W, int n, int p, int L,
                            double* f_mu, double* f_var) {
@@ -663,7 +698,10 @@ static int svgp_run(hipStream_t s, int n, int m, int L, int p, int d, const doub
         return hipGetLastError() == hipSuccess ? 0 : -3;
     }
     const int nve = 512;
-    if (t_side.Yunc)
+    if (t_side.pn)
+        hipLaunchKernelGGL(k_svgp_ve_masked, dim3(nve), dim3(NTHREADS), 0, s, g_mu, g_var, W, Y, (long)ldy, n, p, L,
+                           t_side.mnoise, t_side.pn, S.ve_part);
+    else if (t_side.Yunc)
         hipLaunchKernelGGL(k_svgp_ve_het, dim3(nve), dim3(NTHREADS), 0, s, g_mu, g_var, W, Y, (long)ldy, t_side.Yunc,
                            (long)t_side.ldu, n, p, L, noise, noise_dev, S.ve_part);
     else

@@ -639,6 +639,143 @@ __global__ void k_ve_het_reduce(const double* gw_part, int nwg, const double* W,
     if (j == 0 && e < pl) gW[e] = s1 - scale * W[e] * sv;
 }
 
+// ---------------------------------------------------------------- masked VE backward
+// MaskedGaussian (notebooks/demo: missing output.ipynb, cell 2): a NaN target is a missing observation,
+// and output c has its own variance s2[c] (noise[pn] with pn = p, or one shared entry with pn = 1).
+// The row-tiled shape of k_ve_bwd_het with obs = (y == y) selecting, per entry,
+//   iv = obs ? 1 / s2[c] : 0,   r = obs ? scale (y - f_mu) iv : 0
+// so a missing entry adds an exact 0 to r, alpha, beta, S1, S2 and to its column's noise gradient
+//   dE/ds2[c] = scale sum_n obs (-iv / 2 + ((y - f_mu)^2 + f_var) iv^2 / 2).
+// The last needs a sum over the ROWS of a column: every entry's term goes to a third LDS tile gs[rb][p|1],
+// and thread c adds its column's rb terms in row order into gn_part[workgroup][c].  k_ve_masked_nreduce
+// adds the workgroups' partials in a fixed order (and, with pn = 1, the columns); dE/dW goes through
+// k_ve_het_reduce.  No atomics; every partial is written by its workgroup.
+// LDS: 3 rb (p|1) + 2 L (rb + 1) doubles of row state (<= VH_LDS: rb = 16 rows up to 3 p + 2 L ~ 245, halved
+// beyond) + p (L|1) of W (<= VH_LDS, else W is read from global memory): at most 64 KB with red[].
+int svgp_ve_masked_rows(int p, int l) {
+    int rb = VH_ROWS;
+    while (rb > 0 && (long)rb * 3 * (p | 1) + (long)(rb + 1) * 2 * l > VH_LDS) rb >>= 1;
+    return rb;
+}
+
+__global__ __launch_bounds__(NTHREADS) void k_ve_bwd_masked(const double* g_mu, const double* g_var, const double* W,
+                                                            const double* Y, long ldy, int n, int p, int L,
+                                                            const double* noise, int pn, double scale, int npad,
+                                                            int rb, int w_lds, double* r, double* alpha, double* beta,
+                                                            double* gn_part, double* gw_part) {
+    extern __shared__ double vm_lds[];
+    const int ps = p | 1, ls = L | 1, rs1 = rb + 1, t = threadIdx.x;
+    double* rs = vm_lds;            // [rb][ps] r            (zero where missing and on the rows past n)
+    double* ivs = rs + rb * ps;     // [rb][ps] obs / s2[c]  (likewise)
+    double* gss = ivs + rb * ps;    // [rb][ps] the entry's dE/ds2[c] term (likewise)
+    double* gm = gss + rb * ps;     // [L][rb + 1] g_mu      (zero on the rows past n)
+    double* gv = gm + L * rs1;      // [L][rb + 1] g_var     (likewise)
+    double* Wl = gv + L * rs1;      // [p][ls] W
+    const int n0 = blockIdx.x * rb;
+    const int nr = min(rb, n - n0);   // live rows (<= 0: a workgroup of the padding)
+    for (int e = t; e < L * rb; e += NTHREADS) {
+        const int l = e / rb, i = e % rb;
+        gm[l * rs1 + i] = (i < nr) ? g_mu[(long)l * n + n0 + i] : 0.0;
+        gv[l * rs1 + i] = (i < nr) ? g_var[(long)l * n + n0 + i] : 0.0;
+    }
+    const double* Wp = W;
+    int wld = L;
+    if (W && w_lds) {
+        for (int e = t; e < p * L; e += NTHREADS) Wl[(e / L) * ls + e % L] = W[e];
+        Wp = Wl;
+        wld = ls;
+    }
+    __syncthreads();
+    for (int e = t; e < rb * p; e += NTHREADS) {
+        const int i = e / p, c = e % p;
+        double rv = 0.0, iv = 0.0, gs = 0.0;
+        if (i < nr) {
+            const double y = Y[(long)(n0 + i) * ldy + c];
+            if (y == y) {
+                double fm, fv;
+                if (W) {
+                    fm = 0.0;
+                    fv = 0.0;
+                    for (int l = 0; l < L; ++l) {
+                        const double w = Wp[c * wld + l];
+                        fm += gm[l * rs1 + i] * w;
+                        fv += gv[l * rs1 + i] * (w * w);
+                    }
+                } else {
+                    fm = gm[c * rs1 + i];
+                    fv = gv[c * rs1 + i];
+                }
+                iv = 1.0 / noise[pn == 1 ? 0 : c];
+                const double dy = y - fm;
+                rv = scale * dy * iv;
+                gs = -0.5 * iv + 0.5 * (dy * dy + fv) * iv * iv;
+            }
+            r[(long)(n0 + i) * p + c] = rv;
+        }
+        rs[i * ps + c] = rv;
+        ivs[i * ps + c] = iv;
+        gss[i * ps + c] = gs;
+    }
+    __syncthreads();
+    for (int c = t; c < p; c += NTHREADS) {
+        double s = 0.0;
+        for (int i = 0; i < rb; ++i) s += gss[i * ps + c];
+        gn_part[(long)blockIdx.x * p + c] = scale * s;
+    }
+    for (int e = t; e < L * rb; e += NTHREADS) {
+        const int l = e / rb, i = e % rb;
+        double a = 0.0, b = 0.0;
+        if (W) {
+            for (int c = 0; c < p; ++c) {
+                const double w = Wp[c * wld + l];
+                a += rs[i * ps + c] * w;
+                b += (w * w) * ivs[i * ps + c];
+            }
+        } else {
+            a = rs[i * ps + l];
+            b = ivs[i * ps + l];
+        }
+        alpha[(long)l * npad + n0 + i] = a;
+        beta[(long)l * npad + n0 + i] = (i < nr) ? -0.5 * scale * b : 0.0;
+    }
+    if (!W) return;
+    const long pl = (long)p * L;
+    for (int e = t; e < p * L; e += NTHREADS) {
+        const int c = e / L, l = e % L;
+        double s1 = 0.0, sv = 0.0;
+        for (int i = 0; i < rb; ++i) {
+            s1 += rs[i * ps + c] * gm[l * rs1 + i];
+            sv += gv[l * rs1 + i] * ivs[i * ps + c];
+        }
+        gw_part[2 * blockIdx.x * pl + e] = s1;
+        gw_part[(2 * blockIdx.x + 1) * pl + e] = sv;
+    }
+}
+
+// gnoise[c] = sum_b gn_part[b][c] over the nwg workgroup partials of k_ve_bwd_masked (pn == p): VHR_LANES
+// lanes per column, lane j the partials b = j mod VHR_LANES, a fixed xor tree.  pn == 1: ONE workgroup;
+// thread t adds the columns c = t mod NTHREADS, each over b in order, and block_sum adds the threads.
+__global__ __launch_bounds__(NTHREADS) void k_ve_masked_nreduce(const double* gn_part, int nwg, int p, int pn,
+                                                                double* gnoise) {
+    __shared__ double red[4];
+    if (pn == 1) {
+        double s = 0.0;
+        for (int c = threadIdx.x; c < p; c += NTHREADS)
+            for (int b = 0; b < nwg; ++b) s += gn_part[(long)b * p + c];
+        s = block_sum(s, red);
+        if (threadIdx.x == 0) gnoise[0] = s;
+        return;
+    }
+    const long gt = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    const int c = (int)(gt / VHR_LANES), j = (int)(gt % VHR_LANES);
+    double s = 0.0;
+    if (c < p)
+        for (int b = j; b < nwg; b += VHR_LANES) s += gn_part[(long)b * p + c];
+#pragma unroll
+    for (int o = 1; o < VHR_LANES; o <<= 1) s += __shfl_xor(s, o, 64);
+    if (j == 0 && c < p) gnoise[c] = s;
+}
+
 // ---------------------------------------------------------------- kernel derivative sums
 // For pairs (a in P1 = Z rows, b in P2), weight Wt[a][b] (padded row-major):
 //   gth[q] += sum Wt dk/dtheta_q     (q over [vL, lL(D), vD, lD(D), rho])
@@ -994,9 +1131,12 @@ __global__ void k_grad_reduce(const double* gth_uu, int nb_uu, const double* gth
 // ---------------------------------------------------------------- driver
 struct SvgpGradLayout {
     double *qm, *alpha, *beta, *A, *B, *gA, *Gb, *H, *P, *Sig, *Kbar, *T1, *gLq, *gqm, *r, *gnp, *gth_uu, *gth_uf,
-        *gth_kff, *gz_uu, *gz_uf, *hnp, *hgw;
+        *gth_kff, *gz_uu, *gz_uf, *hnp, *hgw, *mnp;
     int nbc_uu, nbc_uf, n_at, nb_uu, nb_uf, nnoise;
     int het_rb, het_nwg;   // k_ve_bwd_het: rows a workgroup, workgroups (hnp / hgw: its dE/ds2 / dE/dW partials)
+    // k_ve_bwd_masked: the same (mnp: its dE/ds2[c] partials [msk_nwg][p], then one spare entry that takes
+    // k_grad_reduce's scalar noise sum; its dE/dW partials share hgw, sized for the larger count)
+    int msk_rb, msk_nwg;
     size_t bytes;
 };
 
@@ -1043,7 +1183,10 @@ static SvgpGradLayout grad_layout(int nb, int n, int m, int L, int p, int d, siz
     g.het_rb = svgp_ve_het_rows(p, L);
     g.het_nwg = g.het_rb ? npad / g.het_rb : 0;   // npad is a multiple of nb >= 32, rb a power of two <= 16
     g.hnp = take((size_t)g.het_nwg + 8);
-    g.hgw = take((size_t)g.het_nwg * 2 * p * L + 8);
+    g.msk_rb = svgp_ve_masked_rows(p, L);
+    g.msk_nwg = g.msk_rb ? npad / g.msk_rb : 0;
+    g.hgw = take((size_t)std::max(g.het_nwg, g.msk_nwg) * 2 * p * L + 8);
+    g.mnp = take((size_t)g.msk_nwg * p + 8);
     g.bytes = off + 256;
     return g;
 }
@@ -1104,7 +1247,20 @@ static int svgp_grad_run(hipStream_t s, int n, int m, int L, int p, int d, const
     const int G = theta_size(d);
     // 1. VE backward (heteroscedastic: the fused row-tiled kernel and its dE/dW reduction)
     const double* Yunc = svgp_side().Yunc;
-    if (Yunc) {
+    const int pn = svgp_side().pn;
+    if (pn) {
+        if (g.msk_rb == 0) return -4;
+        const int ps = p | 1, ls = L | 1;
+        const int w_lds = (W && (long)p * ls <= VH_LDS) ? 1 : 0;
+        const size_t smem = sizeof(double) * ((size_t)g.msk_rb * 3 * ps + (size_t)(g.msk_rb + 1) * 2 * L +
+                                              (w_lds ? (size_t)p * ls : 0));
+        hipLaunchKernelGGL(k_ve_bwd_masked, dim3(g.msk_nwg), dim3(NTHREADS), smem, s, g_mu, g_var, W, Y, (long)ldy, n, p,
+                           L, svgp_side().mnoise, pn, scale, npad, g.msk_rb, w_lds, g.r, g.alpha, g.beta, g.mnp, g.hgw);
+        if (W) hipLaunchKernelGGL(k_ve_het_reduce, dim3(cdv(p * L * VHR_LANES, 256)), dim3(256), 0, s, g.hgw, g.msk_nwg,
+                                  W, p * L, scale, gW);
+        hipLaunchKernelGGL(k_ve_masked_nreduce, dim3(pn == 1 ? 1 : cdv(p * VHR_LANES, NTHREADS)), dim3(NTHREADS), 0, s,
+                           g.mnp, g.msk_nwg, p, pn, gnoise);
+    } else if (Yunc) {
         if (g.het_rb == 0) return -4;
         const int ps = p | 1, ls = L | 1;
         const int w_lds = (W && (long)p * ls <= VH_LDS) ? 1 : 0;
@@ -1232,9 +1388,12 @@ static int svgp_grad_run(hipStream_t s, int n, int m, int L, int p, int d, const
                        g.gth_kff);
     svgp_join(s);
     const int tot = L * G + m * (d + 1) + 1;
+    // masked: gnoise[pn] is k_ve_masked_nreduce's; the scalar noise sum here is over no partials and goes
+    // to the spare entry behind mnp
+    double* gn_scalar = pn ? g.mnp + (size_t)g.msk_nwg * p : gnoise;
     hipLaunchKernelGGL(k_grad_reduce, dim3(cdv(tot * GR_LANES, 256)), dim3(256), 0, s, g.gth_uu, g.nb_uu, g.gth_uf, g.nb_uf,
                        g.gth_kff, g.gz_uu, g.gz_uf, g.n_at, g.nbc_uu, g.nbc_uf, L, G, d, m, Yunc ? g.hnp : g.gnp,
-                       Yunc ? g.het_nwg : g.nnoise, gtheta, gZ, gnoise);
+                       pn ? 0 : (Yunc ? g.het_nwg : g.nnoise), gtheta, gZ, gn_scalar);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

@@ -403,9 +403,20 @@ class Engine:
         assert Yunc.dim() == 2 and Yunc.shape[0] == n and Yunc.shape[1] >= p, f"Yunc must be [{n}, >= {p}]"
         assert Yunc.stride(1) == 1 and Yunc.stride(0) >= p, "Yunc needs a unit inner stride"
 
-    def svgp_elbo(self, X, Y, Z, thetas, q_mu, q_sqrt, W, noise, scale, jitter=1e-6, Yunc=None):
+    @staticmethod
+    def _check_masked(noise, Y, Yunc, p):
+        """The masked entry points' noise: an fp64 device vector of 1 or p entries; no Yunc with a mask."""
+        assert Yunc is None, "Yunc together with a mask is not supported"
+        assert torch.is_tensor(noise) and noise.dtype == torch.float64, "masked: noise must be a float64 tensor"
+        assert noise.device == Y.device and noise.is_contiguous(), "masked: noise must be contiguous on Y's device"
+        assert noise.numel() in (1, p), f"masked: noise must have 1 or {p} entries, got {noise.numel()}"
+        assert Y.stride(1) == 1 and Y.stride(0) >= p, "Y needs a unit inner stride"
+
+    def svgp_elbo(self, X, Y, Z, thetas, q_mu, q_sqrt, W, noise, scale, jitter=1e-6, Yunc=None, masked=False):
         """SVGP ELBO value; with Yunc [n, >= p] the HeteroscedasticGaussian one (noise + Yunc**2 per
-        observation, mfgp_svgp_elbo_het), where Y may be a row-strided view (the [N, 2P] targets' halves)."""
+        observation, mfgp_svgp_elbo_het), where Y may be a row-strided view (the [N, 2P] targets' halves).
+        masked: the MaskedGaussian one (mfgp_svgp_elbo_masked): NaN targets are missing observations and
+        noise is a DEVICE tensor of 1 or p variances; Y may be a row-strided view."""
         n, dp1 = X.shape
         d = dp1 - 1
         p = Y.shape[1]
@@ -417,6 +428,14 @@ class Engine:
         g_mu = torch.empty((L, n), dtype=torch.float64, device=self.device)
         g_var = torch.empty((L, n), dtype=torch.float64, device=self.device)
         info = torch.empty((L,), dtype=torch.int32, device=self.device)
+        if masked:
+            self._check_masked(noise, Y, Yunc, p)
+            check(self.lib.mfgp_svgp_elbo_masked(self.h, n, m, L, p, d, ptr(X), dp1, ptr(Y), Y.stride(0), ptr(Z),
+                                                 Z.shape[1], ptr(thetas), ptr(q_mu), ptr(q_sqrt), ptr(W), ptr(noise),
+                                                 noise.numel(), float(scale), float(jitter), ptr(ws), ws.numel(),
+                                                 ptr(out), ptr(g_mu), ptr(g_var), ptr(info)),
+                  "mfgp_svgp_elbo_masked")
+            return out, g_mu, g_var, info
         if Yunc is not None:
             self._check_yunc(Yunc, Y, n, p)
             assert Y.stride(1) == 1, "Y needs a unit inner stride"
@@ -436,12 +455,15 @@ class Engine:
         return self._size(self.lib.mfgp_svgp_grad_workspace_size, n, m, L, p, d)
 
     def svgp_elbo_grad(self, X, Y, Z, thetas, q_mu, q_sqrt, W, noise, scale, kl_mult, jitter, out, g_mu, g_var,
-                       gZ, gtheta, gq_mu, gq_sqrt, gW, gnoise, info, ws=None, qs_packed=False, Yunc=None):
+                       gZ, gtheta, gq_mu, gq_sqrt, gW, gnoise, info, ws=None, qs_packed=False, Yunc=None,
+                       masked=False):
         """Gradient of VE*scale - kl_mult*KL w.r.t. the constrained SVGP parameters (all device
         tensors, written in place; noise is a device scalar).  qs_packed: q_sqrt and gq_sqrt are
         packed lower triangles [L, M(M+1)/2] (mfgp_set_svgp_qs_packed), else [L, M, M].  Yunc
         [n, >= p]: the HeteroscedasticGaussian likelihood (mfgp_svgp_elbo_grad_het, which takes
-        qs_packed as an argument, not from the handle)."""
+        qs_packed as an argument, not from the handle).  masked: the MaskedGaussian likelihood
+        (mfgp_svgp_elbo_grad_masked, qs_packed likewise an argument): NaN targets are missing
+        observations, noise and gnoise have 1 or p entries."""
         n, dp1 = X.shape
         d = dp1 - 1
         p = Y.shape[1]
@@ -453,6 +475,17 @@ class Engine:
         elif ws.numel() < nbytes:
             raise MFGPError("svgp_elbo_grad: private workspace too small")
         h = self.h
+        if masked:
+            self._check_masked(noise, Y, Yunc, p)
+            assert gnoise.numel() == noise.numel() and gnoise.is_contiguous(), "masked: gnoise must match noise"
+            check(self.lib.mfgp_svgp_elbo_grad_masked(h, n, m, L, p, d, ptr(X), dp1, ptr(Y), Y.stride(0), ptr(Z), dp1,
+                                                      ptr(thetas), ptr(q_mu), ptr(q_sqrt), 1 if qs_packed else 0,
+                                                      ptr(W), ptr(noise), noise.numel(), float(scale), float(kl_mult),
+                                                      float(jitter), ptr(ws), ws.numel(), ptr(out), ptr(g_mu),
+                                                      ptr(g_var), ptr(gZ), ptr(gtheta), ptr(gq_mu), ptr(gq_sqrt),
+                                                      ptr(gW), ptr(gnoise), ptr(info)),
+                  "mfgp_svgp_elbo_grad_masked")
+            return
         if Yunc is not None:
             self._check_yunc(Yunc, Y, n, p)
             assert Y.stride(1) == 1, "Y needs a unit inner stride"

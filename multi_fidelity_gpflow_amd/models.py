@@ -57,6 +57,20 @@ class HeteroscedasticGaussian(Gaussian):
         self.variance = Parameter(np.reshape(np.asarray(variance, dtype=np.float64), (1,)), transform=positive())
 
 
+class MaskedGaussian(Gaussian):
+    """notebooks/demo: missing output.ipynb, cell 2: a Gaussian likelihood that leaves the NaN entries
+    of Y (missing observations) out of the variational expectations, value and gradients alike.
+    ``variance`` has shape () (one shared variance) or (P,) (one per output; the notebook passes
+    np.ones(P)) under Gaussian's own transform, Shift(1e-6) o Softplus, and is trainable as
+    constructed.  predict_y adds ``variance[None, :]``."""
+
+    def __init__(self, variance=1.0, variance_lower_bound=Gaussian.DEFAULT_VARIANCE_LOWER_BOUND):
+        variance = np.asarray(variance, dtype=np.float64)
+        if variance.ndim > 1:
+            raise ValueError(f"MaskedGaussian: variance must have shape () or (P,), got {list(variance.shape)}")
+        super().__init__(variance, variance_lower_bound)
+
+
 class _ThetaMap:
     """Maps the model's Parameters onto the device theta vector
     [vL, lL(d), vD, lD(d), rho0, noise] of include/mfgp.h."""

@@ -246,7 +246,47 @@ def _assign_exact(p: Parameter, value):
             p.unconstrained_variable = u
             return
         u = np.where(bad, np.nextafter(u, np.where(got < target, np.inf, -np.inf)), u)
-    # no exact neighbour for some entry (a value no forward produces): keep inverse()'s answer
+    # Where |u| is small next to the value (a Softplus value near log 2: u ~ 0), an ulp of u is a
+    # hundredth of an ulp of the value and single-ulp steps do not get there: gallop to a bracket, then
+    # bisect (the transforms are increasing).  Entries with no exact preimage keep inverse()'s answer.
+    u0 = p.unconstrained_variable
+    flat, t = u.reshape(-1), target.reshape(-1)
+    for i in np.flatnonzero(np.asarray(p._fwd(u)).reshape(-1) != t):
+        found = _settle(lambda x: float(np.asarray(p._fwd(np.float64(x)))), float(flat[i]), float(t[i]))
+        flat[i] = np.reshape(u0, -1)[i] if found is None else found
+    p.unconstrained_variable = flat.reshape(u.shape)
+
+
+def _settle(f, a, target):
+    """An x near a with f(x) == target for an increasing f, or None."""
+    fa = f(a)
+    if fa == target:
+        return a
+    up = fa < target
+    step = np.spacing(abs(a)) if a != 0.0 else 5e-324
+    b = a
+    for _ in range(1100):
+        b = a + step if up else a - step
+        fb = f(b)
+        if fb == target:
+            return b
+        if (fb < target) != up:
+            break
+        a, step = b, step * 2.0
+    else:
+        return None
+    for _ in range(1100):
+        mid = a + (b - a) / 2.0
+        if mid == a or mid == b:
+            return None
+        fm = f(mid)
+        if fm == target:
+            return mid
+        if (fm < target) == up:
+            a = mid
+        else:
+            b = mid
+    return None
 
 
 def multiple_assign(module: Module, params: dict):

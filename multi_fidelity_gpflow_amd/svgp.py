@@ -5,6 +5,9 @@
   inducing points, whitened q(u).  ``heterosed=True`` (linear_svgp.py:133-136, :223-267): the
   HeteroscedasticGaussian likelihood over targets [Y_obs | Y_unc] of shape [N, 2P], per-observation
   variance = baseline + Y_unc**2 (mfgp_svgp_elbo_het / mfgp_svgp_elbo_grad_het).
+* ``missing_outputs=True`` on either emulator (notebooks/demo: missing output.ipynb, cell 2): the
+  MaskedGaussian likelihood; NaN entries of Y are missing observations, every output has its own
+  trainable noise variance (mfgp_svgp_elbo_masked / mfgp_svgp_elbo_grad_masked).
 * ``SingleBinSVGP`` — mfgpflow/singlebin_svgp.py:13-135: one LinearMultiFidelityKernel
   per output bin (SeparateIndependent), q_sqrt = 0.1 I.
 
@@ -24,7 +27,7 @@ import torch
 
 from .engine import Engine, theta_size, to_dev
 from .kernels import LinearCoregionalization, LinearMultiFidelityKernel, SeparateIndependent
-from .models import CholeskyError, Gaussian, HeteroscedasticGaussian
+from .models import CholeskyError, Gaussian, HeteroscedasticGaussian, MaskedGaussian
 from .params import (Module, Parameter, Softplus, as_result, gather_entries, multiple_assign, parameter_dict,
                      scatter_entries, tie_entries)
 from .session import _PackedAdam, _Session, check_outcome, span_from_tie
@@ -93,11 +96,23 @@ class _SVGPBase(Module):
         return eng, Z, thetas, q_mu, q_sqrt, W
 
     def _noise(self) -> float:
-        """The likelihood's (baseline) variance as a python float: shape () or (1,)."""
+        """The likelihood's (baseline) variance as a python float: shape () or (1,).  (MaskedGaussian:
+        _noise_vector.)"""
         return float(np.reshape(self.likelihood.variance.numpy(), -1)[0])
 
     def _heteroscedastic(self) -> bool:
         return isinstance(self.likelihood, HeteroscedasticGaussian)
+
+    def _masked(self) -> bool:
+        return isinstance(self.likelihood, MaskedGaussian)
+
+    def _noise_vector(self) -> np.ndarray:
+        """MaskedGaussian's variance as a flat fp64 array of 1 or num_outputs entries (host-side check)."""
+        v = np.ascontiguousarray(np.reshape(self.likelihood.variance.numpy(), -1), dtype=np.float64)
+        if v.size not in (1, self.num_outputs):
+            raise ValueError(f"MaskedGaussian: variance must have shape () or ({self.num_outputs},) = (num_outputs,); "
+                             f"got {list(self.likelihood.variance.shape)}")
+        return v
 
     def _check_targets(self, Y):
         """HeteroscedasticGaussian: the targets are [Y_obs | Y_unc], [N, 2P] (linear_svgp.py:246-249).
@@ -107,6 +122,12 @@ class _SVGPBase(Module):
             if len(shape) != 2 or shape[1] != 2 * P:
                 raise ValueError(f"heteroscedastic targets must have shape [N, {2 * P}] = [N, 2 * num_outputs] "
                                  f"(the observations, then their uncertainties); got {list(shape)}")
+        if self._masked():
+            self._noise_vector()
+            shape, P = tuple(np.shape(Y)), self.num_outputs
+            if len(shape) != 2 or shape[1] != P:
+                raise ValueError(f"masked targets must have shape [N, {P}] = [N, num_outputs] (NaN where an output "
+                                 f"is missing); got {list(shape)}")
 
     def _split_targets(self, Yd):
         """(Y_obs, Y_unc or None): views of the one device tensor, no copy."""
@@ -122,8 +143,13 @@ class _SVGPBase(Module):
         Xd, Yd = to_dev(X, eng.device), to_dev(Y, eng.device)
         Yd, Yunc = self._split_targets(Yd)
         scale = (self.num_data / Xd.shape[0]) if self.num_data else 1.0
-        out, g_mu, g_var, info = eng.svgp_elbo(Xd, Yd, Z, thetas, q_mu, q_sqrt, W, self._noise(), scale,
-                                               DEFAULT_JITTER, Yunc=Yunc)
+        if self._masked():
+            out, g_mu, g_var, info = eng.svgp_elbo(Xd, Yd, Z, thetas, q_mu, q_sqrt, W,
+                                                   to_dev(self._noise_vector(), eng.device), scale, DEFAULT_JITTER,
+                                                   masked=True)
+        else:
+            out, g_mu, g_var, info = eng.svgp_elbo(Xd, Yd, Z, thetas, q_mu, q_sqrt, W, self._noise(), scale,
+                                                   DEFAULT_JITTER, Yunc=Yunc)
         if int(info.max().item()) != 0:
             raise CholeskyError("elbo: Cholesky of K_uu was not successful")
         return out
@@ -163,12 +189,15 @@ class _SVGPBase(Module):
 
     def predict_y(self, Xnew, full_cov=False, full_output_cov=False):
         """GPflow GPModel.predict_y: predict_f plus the Gaussian noise variance (the baseline alone
-        for HeteroscedasticGaussian: Gaussian._predict_mean_and_var reads self.variance)."""
+        for HeteroscedasticGaussian: Gaussian._predict_mean_and_var reads self.variance; each output's
+        own, variance[None, :], for a MaskedGaussian with a (P,) variance)."""
         if full_cov or full_output_cov:
             # GPflow 2.9 GPModel.predict_y (gpflow issue 1461): only the marginal form is supported
             raise NotImplementedError("The predict_y method currently supports only the argument values "
                                       "full_cov=False and full_output_cov=False")
         mean, var = self.predict_f(Xnew)
+        if self._masked():
+            return mean, as_result(var + to_dev(self._noise_vector(), var.device)[None, :])
         return mean, as_result(var + self._noise())
 
     def elbo_and_grad(self, data, kl_multiplier=1.0):
@@ -306,8 +335,11 @@ class _SVGPTrainer(_Session):
         if Wp is not None:
             segs.append(("W", (p, L), Wp.numpy(), Wp.unconstrained_variable, np.full((p, L), Wp.trainable), 0, None))
         nv = model.likelihood.variance
-        segs.append(("noise", (1,), np.reshape(nv.numpy(), (1,)), np.reshape(nv.unconstrained_variable, (1,)),
-                     np.full((1,), nv.trainable), _transform_code(nv), None))
+        # MaskedGaussian: the segment has the variance's own size, 1 or P (one entry per output)
+        self.masked = model._masked()
+        nn = model._noise_vector().size if self.masked else 1
+        segs.append(("noise", (nn,), np.reshape(nv.numpy(), (nn,)), np.reshape(nv.unconstrained_variable, (nn,)),
+                     np.full((nn,), nv.trainable), _transform_code(nv), None))
         self.layout = {}
         off = 0
         cs, us, trs, tfs, sps = [], [], [], [], []
@@ -372,7 +404,8 @@ class _SVGPTrainer(_Session):
                                 self.view(c, "q_sqrt"), W, self.view(c, "noise"), self.scale, self.klm,
                                 DEFAULT_JITTER, self.out, self.g_mu, self.g_var, self.view(g, "Z"),
                                 self.view(g, "theta"), self.view(g, "q_mu"), self.view(g, "q_sqrt"), gW,
-                                self.view(g, "noise"), self.info, ws=self.ws, qs_packed=True, Yunc=self.Yunc)
+                                self.view(g, "noise"), self.info, ws=self.ws, qs_packed=True, Yunc=self.Yunc,
+                                masked=self.masked)
 
     def _step(self):
         self._grad()
@@ -431,7 +464,13 @@ class LatentMFCoregionalizationSVGP(_SVGPBase):
     """mfgpflow/linear_svgp.py:64-151 constructor semantics."""
 
     def __init__(self, X, Y, kernel_L, kernel_delta, num_latents, num_inducing, num_outputs, use_rho=True,
-                 heterosed=False, loss_type='gaussian', w_type='diagonal', window_fraction=0.4, scale=0.2):
+                 heterosed=False, loss_type='gaussian', w_type='diagonal', window_fraction=0.4, scale=0.2, *,
+                 missing_outputs=False):
+        # missing_outputs (notebooks/demo: missing output.ipynb, cell 2): MaskedGaussian with one variance
+        # per output; NaN entries of Y are missing observations
+        if missing_outputs and heterosed:
+            raise ValueError("missing_outputs=True together with heterosed=True is not supported: choose the "
+                             "MaskedGaussian or the HeteroscedasticGaussian likelihood")
         # heterosed (linear_svgp.py:133-139): HeteroscedasticGaussian over targets [Y_obs | Y_unc] of
         # shape [N, 2 num_outputs]; the Poisson variant is a stub in the reference itself
         if heterosed and loss_type == 'poisson':
@@ -443,6 +482,9 @@ class LatentMFCoregionalizationSVGP(_SVGPBase):
         self.num_latents = num_latents
         self.loss_type = loss_type
         if w_type == 'pca':
+            if missing_outputs and np.isnan(np.asarray(Y, dtype=np.float64)).any():
+                raise ValueError("w_type='pca' needs complete targets: PCA cannot be fitted to Y with NaN entries; "
+                                 "use w_type='diagonal' with missing_outputs=True")
             W = Parameter(initialize_W_pca(np.asarray(Y)[:, :num_outputs], num_outputs, num_latents))
         elif w_type == 'diagonal':
             W = Parameter(initialize_W(num_outputs, num_latents, window_fraction=window_fraction, scale=scale))
@@ -456,7 +498,8 @@ class LatentMFCoregionalizationSVGP(_SVGPBase):
         Z = kmeans_inducing(np.asarray(X), num_inducing, 42)
         M = Z.shape[0]
         self._setup(Z, np.zeros((M, num_latents)), np.tile(np.eye(M)[None], (num_latents, 1, 1)),
-                    HeteroscedasticGaussian(variance=np.array([1.0])) if heterosed else Gaussian(variance=1.0),
+                    MaskedGaussian(variance=np.ones(num_outputs)) if missing_outputs else
+                    (HeteroscedasticGaussian(variance=np.array([1.0])) if heterosed else Gaussian(variance=1.0)),
                     np.asarray(X).shape[0])
         self.kl_history = []
 
@@ -480,12 +523,12 @@ class LatentMFCoregionalizationSVGP(_SVGPBase):
         super().save_model(filename)
 
     @staticmethod
-    def load_model(filename, *args):
-        """linear_svgp.py:214-221: rebuild with the constructor arguments, then
-        multiple_assign the saved parameter_dict."""
+    def load_model(filename, *args, **kwargs):
+        """linear_svgp.py:214-221: rebuild with the constructor arguments (the caller gives heterosed /
+        missing_outputs again), then multiple_assign the saved parameter_dict."""
         with open(filename, "rb") as f:
             params = pickle.load(f)
-        model = LatentMFCoregionalizationSVGP(*args)
+        model = LatentMFCoregionalizationSVGP(*args, **kwargs)
         multiple_assign(model, params)
         return model
 
@@ -494,7 +537,8 @@ class SingleBinSVGP(_SVGPBase):
     """mfgpflow/singlebin_svgp.py:20-62 constructor semantics (Z values are ignored;
     KMeans is recomputed with Z.shape[0] clusters, singlebin_svgp.py:50-51)."""
 
-    def __init__(self, X, Y, kernel_L, kernel_delta, num_outputs, Z, random_state=42):
+    def __init__(self, X, Y, kernel_L, kernel_delta, num_outputs, Z, random_state=42, *, missing_outputs=False):
+        # missing_outputs: as LatentMFCoregionalizationSVGP's (MaskedGaussian, one variance per bin)
         self.num_outputs = num_outputs
         kernels = [LinearMultiFidelityKernel(copy.deepcopy(kernel_L), copy.deepcopy(kernel_delta), num_output_dims=1)
                    for _ in range(num_outputs)]
@@ -502,7 +546,7 @@ class SingleBinSVGP(_SVGPBase):
         Zi = kmeans_inducing(np.asarray(X), np.asarray(Z).shape[0], random_state)
         M = Zi.shape[0]
         self._setup(Zi, np.zeros((M, num_outputs)), np.repeat(np.eye(M)[None], num_outputs, axis=0) * 0.1,
-                    Gaussian(), None)
+                    MaskedGaussian(variance=np.ones(num_outputs)) if missing_outputs else Gaussian(), None)
 
     def optimize(self, data, max_iters=10000, initial_lr=0.01, unfix_noise_after=5000, verbose=False, graph=True,
                  graph_chunk=50):
@@ -515,8 +559,8 @@ class SingleBinSVGP(_SVGPBase):
         super().save_model(filename)
 
     @staticmethod
-    def load_model(filename, X, Y, kernel_L, kernel_delta, num_outputs, Z):
-        model = SingleBinSVGP(X, Y, kernel_L, kernel_delta, num_outputs, Z)
+    def load_model(filename, X, Y, kernel_L, kernel_delta, num_outputs, Z, *, missing_outputs=False):
+        model = SingleBinSVGP(X, Y, kernel_L, kernel_delta, num_outputs, Z, missing_outputs=missing_outputs)
         with open(filename, "rb") as f:
             multiple_assign(model, pickle.load(f))
         return model
