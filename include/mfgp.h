@@ -365,6 +365,43 @@ int mfgp_svgp_predict(mfgp_handle_t h, int nstar, int m, int l, int p, int d, co
                       const double* W, double jitter, void* ws, size_t ws_bytes, double* g_mu, double* g_var,
                       double* f_mu, double* f_var, int* info);
 
+/* ---- Cached posterior (GPflow model.posterior()): the X*-independent work of predict_f done once.
+ * A cache is a self-contained device block (training inputs / inducing points, kernel parameters,
+ * inverse factor, projected targets): the predict calls read nothing else of the model, run no
+ * Gram of X, no factorization, write no info and allocate nothing.  The block is laid out for the
+ * handle's tile size (mfgp_set_tile) at build time; predict with the same tile size.  Two predict
+ * calls with the same inputs return the same bits (fixed-order sums, no floating-point atomics).
+ *
+ * GPR (nlf = 0: LinearMultiFidelityKernel, fp64; nlf = m: graph kernel with m LF sources):
+ *   build    runs the Gram + factor of mfgp_gpr_predict once and stores X, theta, L^{-1} (lower
+ *            tiles) and Z = L^{-1} Y.  ws: at least mfgp_gpr_predict_cov_workspace_size(h, nlf, n, p,
+ *            d, 1) bytes.  info as mfgp_gpr_predict (nonzero: the cache is not usable).
+ *   predict  A = L^{-1} K(X, X*) with K generated inside the product kernel, mean [nstar x p] (ldm)
+ *            = A^T Z, var [nstar] = K_diag(X*) - colsum(A^2); cov (may be NULL) [nstar x nstar] (ldc)
+ *            = K(X*, X*) - A^T A.  Two launches when cov is NULL.
+ * A cache or workspace smaller than the *_size calls report: MFGP_ERR_WORKSPACE, before any device work. */
+int mfgp_gpr_posterior_size(mfgp_handle_t h, int nlf, int n, int p, int d, size_t* bytes);
+int mfgp_gpr_posterior_build(mfgp_handle_t h, int nlf, int n, int p, int d, const double* X, int ldx, const double* Y,
+                             int ldy, const double* theta, void* ws, size_t ws_bytes, void* cache, size_t cache_bytes,
+                             int* info);
+int mfgp_gpr_posterior_predict_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar,
+                                              size_t* bytes);
+int mfgp_gpr_posterior_predict(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar, const void* cache,
+                               size_t cache_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes, double* mean,
+                               int ldm, double* var, double* cov, int ldc);
+/* SVGP (arguments as mfgp_svgp_predict): build factors every K_uu and stores Z, thetas, W, q_mu,
+ * Lm^{-1} and C = tril(q_sqrt)^T Lm^{-1} per latent (ws: at least mfgp_svgp_workspace_size(h, 1, m, l,
+ * p, d) bytes; info [l]).  predict writes the marginal f_mu / f_var [nstar][p] of mfgp_svgp_predict;
+ * mixed: 1 when the cache was built with a W (LinearCoregionalization), 0 for independent outputs. */
+int mfgp_svgp_posterior_size(mfgp_handle_t h, int m, int l, int p, int d, size_t* bytes);
+int mfgp_svgp_posterior_build(mfgp_handle_t h, int m, int l, int p, int d, const double* Z, int ldz,
+                              const double* thetas, const double* q_mu, const double* q_sqrt, const double* W,
+                              double jitter, void* ws, size_t ws_bytes, void* cache, size_t cache_bytes, int* info);
+int mfgp_svgp_posterior_predict_workspace_size(mfgp_handle_t h, int nstar, int m, int l, int p, int d, size_t* bytes);
+int mfgp_svgp_posterior_predict(mfgp_handle_t h, int nstar, int m, int l, int p, int d, int mixed, const void* cache,
+                                size_t cache_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes,
+                                double* f_mu, double* f_var);
+
 /* Diagnostic: one v_mfma_f64_16x16x4_f64 with A[i][k] = 4i+k+1, B[k][j] = 100k+j;
  * writes C (16x16 row-major, device). */
 int mfgp_selftest_mfma(mfgp_handle_t h, double* out);

@@ -811,6 +811,224 @@ static int f32_predict(mfgp_handle_t h, int n, int p, int d, int ns, const float
     return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
 }
 
+// ---------------------------------------------------------------- cached posterior (mfgp_posterior.hip)
+// GPR cache (self-contained, laid out for the tile size it was built with):
+//   [X: n x (d + 1), dense][theta: G][LZ: Npad x (Npad + Ppad) = the factor's Xo rows, L^{-1} lower tiles | Z = L^{-1} Y]
+struct GprCache {
+    int npad, T, ppad, Tp, G;
+    long ldr;
+    double *X, *theta, *LZ;
+    size_t bytes;
+};
+static GprCache gpr_cache_layout(int nb, int nlf, int n, int p, int d, void* base) {
+    GprCache c;
+    c.T = ceil_div(n, nb);
+    c.npad = c.T * nb;
+    c.Tp = ceil_div(p, nb);
+    c.ppad = c.Tp * nb;
+    c.G = kernel_theta_size(nlf, d);
+    c.ldr = (long)c.npad + c.ppad;
+    Carve cv(base);
+    c.X = cv.take<double>((size_t)n * (d + 1));
+    c.theta = cv.take<double>((size_t)c.G);
+    c.LZ = cv.take<double>((size_t)c.npad * c.ldr);
+    c.bytes = cv.off + 256;
+    return c;
+}
+
+// m-tiles per k_post_a task.  A batch that fills the device with whole rows keeps them whole (no
+// partials to re-read); otherwise rows are cut so that the longest task is 8 tile products (a row
+// of up to 64 tiles then has at most 8 partials: one batch of loads in k_post_out).
+constexpr int POST_CHUNK = 8;
+static int post_chunk(int T, int Ts, int batch) { return (long)batch * T * Ts >= 256 ? T : POST_CHUNK; }
+
+struct PostLayout {
+    int Ts, nspad, chunk, ntask, ngrp;
+    double *Apart, *Bpart, *mpart, *vpart, *Am, *Kss, *Cov;   // GPR
+    double *pa, *pb, *pm, *gm, *gv;                           // SVGP
+    int* cnt;
+    size_t bytes;
+};
+// svgp: batch = latents, T = Tm; gpr: batch = 1
+static PostLayout post_layout(int nb, int T, int Tp, int nstar, int batch, bool svgp, void* ws) {
+    PostLayout P{};
+    P.Ts = ceil_div(nstar > 0 ? nstar : 1, nb);
+    P.nspad = P.Ts * nb;
+    P.chunk = post_chunk(T, P.Ts, batch);
+    P.ntask = post_ntasks(T, P.chunk, svgp ? 1 : 0);
+    P.ngrp = ceil_div(T, post_rg(nb));
+    Carve c(ws);
+    const size_t part = (size_t)batch * P.ntask * P.Ts * nb * nb;
+    P.Apart = c.take<double>(part);
+    P.cnt = c.take<int>((size_t)P.Ts);
+    if (svgp) {
+        P.Bpart = c.take<double>(part);
+        const size_t pp = (size_t)batch * P.ngrp * P.nspad;
+        P.pa = c.take<double>(pp);
+        P.pb = c.take<double>(pp);
+        P.pm = c.take<double>(pp);
+        P.gm = c.take<double>((size_t)batch * P.nspad);
+        P.gv = c.take<double>((size_t)batch * P.nspad);
+    } else {
+        P.mpart = c.take<double>((size_t)P.ngrp * P.nspad * Tp * nb);
+        P.vpart = c.take<double>((size_t)P.ngrp * P.nspad);
+        P.Am = c.take<double>((size_t)T * nb * P.nspad);
+        P.Kss = c.take<double>((size_t)P.nspad * P.nspad);
+        P.Cov = c.take<double>((size_t)P.nspad * P.nspad);
+    }
+    P.bytes = c.off + 256;
+    return P;
+}
+
+template <int NB>
+static int gpr_posterior_build_impl(mfgp_handle_t h, int nlf, int n, int p, int d, const double* X, int ldx,
+                                    const double* Y, int ldy, const double* theta, void* ws, size_t ws_bytes,
+                                    void* cache, size_t cache_bytes, int* info) {
+    const GprLayout L = gpr_layout(NB, n, p, d, ws, h->grad_chunk, nlf);
+    const GprCache c = gpr_cache_layout(NB, nlf, n, p, d, cache);
+    if (ws_bytes < L.bytes || cache_bytes < c.bytes) return MFGP_ERR_WORKSPACE;
+    hipStream_t s = h->stream;
+    gram_lml_and_factor<NB>(s, L, n, p, d, X, ldx, Y, ldy, theta, info, nlf);
+    auto copy = [&](const double* src, long lds, double* dst, long ldd, int rows, int cols) {
+        const long tot = (long)rows * cols;
+        hipLaunchKernelGGL(k_copy_block, dim3((int)std::min<long>((tot + 255) / 256, 2048)), dim3(256), 0, s, src, lds,
+                           dst, ldd, rows, cols);
+    };
+    copy(X, ldx, c.X, d + 1, n, d + 1);
+    copy(theta, c.G, c.theta, c.G, 1, c.G);
+    copy(L.Xo, c.ldr, c.LZ, c.ldr, c.npad, (int)c.ldr);
+    return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
+}
+
+template <int NB>
+static int gpr_posterior_predict_impl(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar, const void* cache,
+                                      size_t cache_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes,
+                                      double* mean, int ldm, double* var, double* cov, int ldc) {
+    const GprCache c = gpr_cache_layout(NB, nlf, n, p, d, const_cast<void*>(cache));
+    const PostLayout P = post_layout(NB, c.T, c.Tp, nstar, 1, false, ws);
+    if (cache_bytes < c.bytes || ws_bytes < P.bytes) return MFGP_ERR_WORKSPACE;
+    hipStream_t s = h->stream;
+    PostArgs a{};
+    a.Li = c.LZ; a.ldl = c.ldr; a.sL = 0;
+    a.X1 = c.X; a.ldx1 = d + 1; a.n1 = n;
+    a.theta = c.theta; a.stheta = 0;
+    a.Xs = Xs; a.ldxs = ldxs; a.nstar = nstar;
+    a.D = d; a.nlf = nlf;
+    a.T = c.T; a.Ts = P.Ts; a.chunk = P.chunk; a.full = 0; a.ntask = P.ntask; a.ngrp = P.ngrp;
+    a.Apart = P.Apart; a.cnt = P.cnt;
+    a.Zc = c.LZ + c.npad; a.ldz = c.ldr; a.Tp = c.Tp; a.p = p;
+    a.Am = cov ? P.Am : nullptr; a.ldam = P.nspad;
+    a.mpart = P.mpart; a.vpart = P.vpart;
+    a.mean = mean; a.ldm = ldm; a.var = var;
+    launch_post<NB>(a, 1, s);
+    if (cov) {
+        // base_conditional(full_cov=True): Kss - A^T A, as the tail of predict_impl (theta from the cache)
+        if (nlf) (void)hipMemsetAsync(P.Kss, 0, sizeof(double) * (size_t)P.nspad * P.nspad, s);
+        GramArgs gs{};
+        gs.X1 = Xs; gs.ldx1 = ldxs; gs.n1 = nstar;
+        gs.X2 = Xs; gs.ldx2 = ldxs; gs.n2 = nstar;
+        gs.theta = c.theta; gs.D = d; gs.rbf_only = 0;
+        gs.out = P.Kss; gs.ldo = P.nspad; gs.padded = 0; gs.tiles_c = P.Ts; gs.nlf = nlf;
+        gs.diag_add = nlf ? GRAPH_JITTER : 0.0;
+        if (nlf) launch_gram<NB>(gs, P.Ts * P.Ts, 1, s);
+        else launch_gram_dense(gs, 1, P.nspad, P.nspad, s);
+        BgemmArgs b{};
+        b.A = P.Am; b.lda = P.nspad;
+        b.B = P.Am; b.ldb = P.nspad;
+        b.Cin = P.Kss; b.ldc = P.nspad; b.beta = 1.0;
+        b.D = P.Cov; b.ldd = P.nspad;
+        b.alpha = -1.0;
+        b.Mt = P.Ts; b.Nt = P.Ts; b.Kt = c.T;
+        launch_bgemm(NB, s, 1, 0, b, 1);
+        const long tot = (long)nstar * nstar;
+        hipLaunchKernelGGL(k_copy_block, dim3((int)std::min<long>((tot + 255) / 256, 2048)), dim3(256), 0, s, P.Cov,
+                           (long)P.nspad, cov, (long)ldc, nstar, nstar);
+    }
+    return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
+}
+
+// SVGP cache: [Z: m x (d + 1)][thetas: l x G][W: p x l][q_mu^T: l x Mpad, zero padded]
+//             [Lm^{-1}: l x Mpad x Mpad][C = Lq^T Lm^{-1}: l x Mpad x Mpad]
+struct SvgpCache {
+    int Tm, mpad, G;
+    double *Z, *thetas, *W, *qmu, *Li, *C;
+    size_t bytes;
+};
+static SvgpCache svgp_cache_layout(int nb, int m, int l, int p, int d, void* base) {
+    SvgpCache c;
+    c.Tm = ceil_div(m, nb);
+    c.mpad = c.Tm * nb;
+    c.G = theta_size(d);
+    const size_t mm = (size_t)c.mpad * c.mpad;
+    Carve cv(base);
+    c.Z = cv.take<double>((size_t)m * (d + 1));
+    c.thetas = cv.take<double>((size_t)l * c.G);
+    c.W = cv.take<double>((size_t)p * l);
+    c.qmu = cv.take<double>((size_t)l * c.mpad);
+    c.Li = cv.take<double>(mm * l);
+    c.C = cv.take<double>(mm * l);
+    c.bytes = cv.off + 256;
+    return c;
+}
+
+// q_mu [m][L] -> [L][Mpad], zero padded
+__global__ void k_post_qmu_pad(const double* q_mu, int m, int L, int mpad, double* out) {
+    const long total = (long)L * mpad;
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const int l = (int)(e / mpad), r = (int)(e % mpad);
+        out[e] = r < m ? q_mu[(long)r * L + l] : 0.0;
+    }
+}
+
+static int svgp_posterior_build_impl(mfgp_handle_t h, int m, int l, int p, int d, const double* Z, int ldz,
+                                     const double* thetas, const double* q_mu, const double* q_sqrt, const double* W,
+                                     double jitter, void* ws, size_t ws_bytes, void* cache, size_t cache_bytes,
+                                     int* info) {
+    const SvgpCache c = svgp_cache_layout(h->nb, m, l, p, d, cache);
+    if (cache_bytes < c.bytes || ws_bytes < svgp_posterior_factor_bytes(h->nb, m, l)) return MFGP_ERR_WORKSPACE;
+    hipStream_t s = h->stream;
+    const int rc = svgp_posterior_factor(s, h->nb, m, l, d, Z, ldz, thetas, q_sqrt, jitter, ws, ws_bytes, c.Li, c.C,
+                                         info);
+    if (rc) return rc == -2 ? MFGP_ERR_WORKSPACE : MFGP_ERR_LAUNCH;
+    auto copy = [&](const double* src, long lds, double* dst, long ldd, int rows, int cols) {
+        const long tot = (long)rows * cols;
+        hipLaunchKernelGGL(k_copy_block, dim3((int)std::min<long>((tot + 255) / 256, 2048)), dim3(256), 0, s, src, lds,
+                           dst, ldd, rows, cols);
+    };
+    copy(Z, ldz, c.Z, d + 1, m, d + 1);
+    copy(thetas, c.G, c.thetas, c.G, l, c.G);
+    if (W) copy(W, l, c.W, l, p, l);
+    const long tot = (long)l * c.mpad;
+    hipLaunchKernelGGL(k_post_qmu_pad, dim3((int)std::min<long>((tot + 255) / 256, 2048)), dim3(256), 0, s, q_mu, m, l,
+                       c.mpad, c.qmu);
+    return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
+}
+
+static int svgp_posterior_predict_impl(mfgp_handle_t h, int nstar, int m, int l, int p, int d, int mixed,
+                                       const void* cache, size_t cache_bytes, const double* Xs, int ldxs, void* ws,
+                                       size_t ws_bytes, double* f_mu, double* f_var) {
+    const SvgpCache c = svgp_cache_layout(h->nb, m, l, p, d, const_cast<void*>(cache));
+    const PostLayout P = post_layout(h->nb, c.Tm, 0, nstar, l, true, ws);
+    if (cache_bytes < c.bytes || ws_bytes < P.bytes) return MFGP_ERR_WORKSPACE;
+    const long mm = (long)c.mpad * c.mpad;
+    PostArgs a{};
+    a.Li = c.Li; a.ldl = c.mpad; a.sL = mm;
+    a.C = c.C; a.ldc = c.mpad; a.sC = mm;
+    a.X1 = c.Z; a.ldx1 = d + 1; a.n1 = m;
+    a.theta = c.thetas; a.stheta = c.G;
+    a.Xs = Xs; a.ldxs = ldxs; a.nstar = nstar;
+    a.D = d; a.nlf = 0;
+    a.T = c.Tm; a.Ts = P.Ts; a.chunk = P.chunk; a.full = 1; a.ntask = P.ntask; a.ngrp = P.ngrp;
+    a.Apart = P.Apart; a.Bpart = P.Bpart; a.cnt = P.cnt;
+    a.p = p;
+    a.qmu = c.qmu; a.pa = P.pa; a.pb = P.pb; a.pm = P.pm; a.gm = P.gm; a.gv = P.gv;
+    a.W = mixed ? c.W : nullptr;
+    a.f_mu = f_mu; a.f_var = f_var;
+    if (h->nb == 64) launch_post<64>(a, l, h->stream);
+    else launch_post<32>(a, l, h->stream);
+    return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
+}
+
 }  // namespace mfgp
 
 using namespace mfgp;
@@ -1448,6 +1666,94 @@ int mfgp_svgp_predict_cov(mfgp_handle_t h, int mode, int nstar, int m, int l, in
     const int rc = svgp_predict_cov_impl(h->stream, h->nb, mode, nstar, m, l, p, d, Xs, ldxs, Z, ldz, thetas, q_mu,
                                          q_sqrt, W, jitter, ws, ws_bytes, g_mu, g_var, f_mu, f_var, f_cov, info);
     return rc == -2 ? MFGP_ERR_WORKSPACE : (rc ? MFGP_ERR_LAUNCH : MFGP_OK);
+}
+
+// ---------------------------------------------------------------- cached posterior
+int mfgp_gpr_posterior_size(mfgp_handle_t h, int nlf, int n, int p, int d, size_t* bytes) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nlf < 0 || nlf > MFGP_MAX_LF || n < 1 || p < 1 || !bytes) return MFGP_ERR_ARG;
+    *bytes = gpr_cache_layout(h->nb, nlf, n, p, d, nullptr).bytes;
+    return MFGP_OK;
+}
+
+int mfgp_gpr_posterior_build(mfgp_handle_t h, int nlf, int n, int p, int d, const double* X, int ldx, const double* Y,
+                             int ldy, const double* theta, void* ws, size_t ws_bytes, void* cache, size_t cache_bytes,
+                             int* info) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nlf < 0 || nlf > MFGP_MAX_LF) return MFGP_ERR_ARG;
+    if (n < 1 || p < 1 || !X || !Y || !theta || !ws || !cache || !info || ldx < d + 1 || ldy < p) return MFGP_ERR_ARG;
+    if (h->nb == 64)
+        return gpr_posterior_build_impl<64>(h, nlf, n, p, d, X, ldx, Y, ldy, theta, ws, ws_bytes, cache, cache_bytes,
+                                            info);
+    return gpr_posterior_build_impl<32>(h, nlf, n, p, d, X, ldx, Y, ldy, theta, ws, ws_bytes, cache, cache_bytes, info);
+}
+
+int mfgp_gpr_posterior_predict_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar,
+                                              size_t* bytes) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nlf < 0 || nlf > MFGP_MAX_LF || n < 1 || p < 1 || nstar < 1 || !bytes) return MFGP_ERR_ARG;
+    const GprCache c = gpr_cache_layout(h->nb, nlf, n, p, d, nullptr);
+    *bytes = post_layout(h->nb, c.T, c.Tp, nstar, 1, false, nullptr).bytes;
+    return MFGP_OK;
+}
+
+int mfgp_gpr_posterior_predict(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar, const void* cache,
+                               size_t cache_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes, double* mean,
+                               int ldm, double* var, double* cov, int ldc) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nlf < 0 || nlf > MFGP_MAX_LF) return MFGP_ERR_ARG;
+    if (n < 1 || p < 1 || nstar < 1 || !cache || !Xs || !ws || !mean || !var || ldxs < d + 1 || ldm < p)
+        return MFGP_ERR_ARG;
+    if (cov && ldc < nstar) return MFGP_ERR_ARG;
+    if (h->nb == 64)
+        return gpr_posterior_predict_impl<64>(h, nlf, n, p, d, nstar, cache, cache_bytes, Xs, ldxs, ws, ws_bytes, mean,
+                                              ldm, var, cov, ldc);
+    return gpr_posterior_predict_impl<32>(h, nlf, n, p, d, nstar, cache, cache_bytes, Xs, ldxs, ws, ws_bytes, mean,
+                                          ldm, var, cov, ldc);
+}
+
+int mfgp_svgp_posterior_size(mfgp_handle_t h, int m, int l, int p, int d, size_t* bytes) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (m < 1 || l < 1 || p < 1 || !bytes) return MFGP_ERR_ARG;
+    *bytes = svgp_cache_layout(h->nb, m, l, p, d, nullptr).bytes;
+    return MFGP_OK;
+}
+
+int mfgp_svgp_posterior_build(mfgp_handle_t h, int m, int l, int p, int d, const double* Z, int ldz,
+                              const double* thetas, const double* q_mu, const double* q_sqrt, const double* W,
+                              double jitter, void* ws, size_t ws_bytes, void* cache, size_t cache_bytes, int* info) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (m < 1 || l < 1 || p < 1 || !Z || !thetas || !q_mu || !q_sqrt || !ws || !cache || !info || ldz < d + 1)
+        return MFGP_ERR_ARG;
+    if (!W && l != p) return MFGP_ERR_ARG;
+    return svgp_posterior_build_impl(h, m, l, p, d, Z, ldz, thetas, q_mu, q_sqrt, W, jitter, ws, ws_bytes, cache,
+                                     cache_bytes, info);
+}
+
+int mfgp_svgp_posterior_predict_workspace_size(mfgp_handle_t h, int nstar, int m, int l, int p, int d, size_t* bytes) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nstar < 1 || m < 1 || l < 1 || p < 1 || !bytes) return MFGP_ERR_ARG;
+    *bytes = post_layout(h->nb, ceil_div(m, h->nb), 0, nstar, l, true, nullptr).bytes;
+    return MFGP_OK;
+}
+
+int mfgp_svgp_posterior_predict(mfgp_handle_t h, int nstar, int m, int l, int p, int d, int mixed, const void* cache,
+                                size_t cache_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes,
+                                double* f_mu, double* f_var) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nstar < 1 || m < 1 || l < 1 || p < 1 || !cache || !Xs || !ws || !f_mu || !f_var || ldxs < d + 1)
+        return MFGP_ERR_ARG;
+    if (!mixed && l != p) return MFGP_ERR_ARG;
+    return svgp_posterior_predict_impl(h, nstar, m, l, p, d, mixed, cache, cache_bytes, Xs, ldxs, ws, ws_bytes, f_mu,
+                                       f_var);
 }
 
 int mfgp_selftest_mfma(mfgp_handle_t h, double* out) {

@@ -166,6 +166,49 @@ struct PredOutArgs {
     int T, Tp, nstar, p;
 };
 
+// Cached-posterior predict (mfgp_posterior.hip): A = L^{-1} K(X1, X*) against a cached inverse
+// factor, K generated tile by tile in LDS.  Two launches: k_post_a (partial row products, one
+// task = one row tile x `chunk` m-tiles) and k_post_out (fixed-order sum of a row tile's partials,
+// its moment partials, and the last-arriving workgroup of a column tile writes the outputs).
+// GPR (Zc != nullptr): mean = A^T Z, var = K_diag(X*) - colsum(A^2).  SVGP (qmu != nullptr), batched
+// over latents: also B = C K (C = Lq^T Lm^{-1}, full rows), g_mu = A^T q_mu,
+// g_var = Kff - colsum(A^2) + colsum(B^2), then the output mixing.
+struct PostArgs {
+    const double* Li; long ldl; long sL;      // L^{-1}, lower tiles (row-major), batch stride
+    const double* C; long ldc; long sC;       // SVGP: Lq^T Lm^{-1} (all tiles); nullptr: none
+    const double* X1; long ldx1; int n1;      // cached training inputs / inducing points [n1, D + 1]
+    const double* theta; long stheta;         // cached kernel parameters, per batch entry
+    const double* Xs; long ldxs; int nstar;
+    int D, nlf;
+    int T, Ts, chunk, full;                   // row tiles, column tiles, m-tiles per task, full rows (C)
+    int ntask;                                // tasks per batch entry (post_ntasks)
+    int ngrp;                                 // k_post_out workgroups per column tile: ceil(T / post_rg(NB)) row groups
+    double* Apart; double* Bpart;             // [batch][ntask][Ts][NB * NB]
+    int* cnt;                                 // Ts arrival counters (zeroed by k_post_a)
+    // GPR outputs
+    const double* Zc; long ldz; int Tp, p;    // Z = L^{-1} Y tiles (cached)
+    double* Am; long ldam;                    // full_cov: A (Npad x Nspad); nullptr: not kept
+    double* mpart;                            // [ngrp][Nspad][Ppad] mean partials
+    double* vpart;                            // [ngrp][Nspad] colsum(A^2) partials
+    double* mean; long ldm; double* var;
+    // SVGP outputs
+    const double* qmu;                        // [batch][Mpad] cached q_mu columns (zero padded)
+    double *pa, *pb, *pm;                     // [batch][ngrp][Nspad] partials
+    double *gm, *gv;                          // [batch][Nspad] latent moments
+    const double* W;                          // mixing [p][batch]; nullptr: identity (batch == p)
+    double* f_mu; double* f_var;              // [nstar][p]
+};
+// tasks of one batch entry: row tile i has ceil((full ? T : i + 1) / chunk) of them
+int post_ntasks(int T, int chunk, int full);
+// row tiles one k_post_out workgroup takes (128 rows: its A tiles stay in LDS across the output tiles)
+constexpr int post_rg(int nb) { return nb == 32 ? 4 : 2; }
+template <int NB> void launch_post(const PostArgs& a, int batch, hipStream_t s);
+// tril(q_sqrt) zero padded / C = Lq^T Linv of the SVGP K_uu pipeline, into caller buffers (mfgp_svgp.hip)
+int svgp_posterior_factor(hipStream_t s, int nb, int m, int l, int d, const double* Z, int ldz, const double* thetas,
+                          const double* q_sqrt, double jitter, void* ws, size_t ws_bytes, double* Li, double* C,
+                          int* info);
+size_t svgp_posterior_factor_bytes(int nb, int m, int l);
+
 // Batched fp64 MFMA GEMM (k_bgemm, mfgp_svgp_grad.hip), NB x NB output tiles:
 // D = (alpha * op(A) diag(s) op(B) + beta * Cin) [* diag(colscale)] + x y^T   (tril: zero j > i)
 struct BgemmArgs {

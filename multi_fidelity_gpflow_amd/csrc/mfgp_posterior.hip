@@ -1,0 +1,391 @@
+// Cached-posterior predict (GPflow model.posterior()): the work of predict_f that depends on X*.
+//
+//   k_post_a    partial products of A = L^{-1} K(X, X*) against the CACHED inverse factor.  The
+//               K(X, X*) tile of every step is generated in LDS from the cached X rows and the X*
+//               rows (linear MF / graph entry function, theta from the cache): K_mn never exists in
+//               HBM.  One task = one row tile x `chunk` consecutive m-tiles, so the long last rows
+//               of the triangular product are spread over workgroups (PostArgs, mfgp_internal.h).
+//   k_post_out  per (group of 128 rows, column tile): each row tile's partials summed in task order,
+//               then the group's moment partials (sum_i A_i^T Z_i, colsum(A_i^2); SVGP:
+//               colsum(B_i^2), A_i^T q_mu).  The last workgroup to arrive at a column tile's counter
+//               sums the group partials in group order, folds in K_diag(X*) and writes the outputs
+//               (SVGP: latent moments, mixing).
+//
+// Every sum has a fixed order and there are no floating-point atomics: two calls with the same
+// inputs give the same bits.  Cross-workgroup data inside k_post_out goes through sc1 stores /
+// loads (st_coherent / ld_coherent), the producer drains its stores before the arrival atomic.
+#include "mfgp_device.h"
+#include "mfgp_internal.h"
+
+namespace mfgp {
+
+constexpr int PMAXD = 32;
+constexpr int PXS = PMAXD + 1;   // LDS row stride of staged inputs (odd: distinct banks over rows)
+constexpr int PTHETA = 192;      // theta entries staged in LDS (graph kernel, 4 sources, D = 32: 186)
+
+int post_ntasks(int T, int chunk, int full) {
+    int n = 0;
+    for (int i = 0; i < T; ++i) n += ((full ? T : i + 1) + chunk - 1) / chunk;
+    return n;
+}
+
+// row tile i: its first task and its task count
+__device__ __forceinline__ void post_row_tasks(int T, int chunk, int full, int i, int& base, int& nch) {
+    base = 0;
+    for (int j = 0; j < i; ++j) base += ((full ? T : j + 1) + chunk - 1) / chunk;
+    nch = ((full ? T : i + 1) + chunk - 1) / chunk;
+}
+
+// The NB x NB tile K(x1 rows, xs rows) of the linear multi-fidelity kernel into Ks.  A thread owns
+// column c = t % NB of rows t / NB + (NTHREADS / NB) q and works on four of its entries at a time:
+// the four distance sums share the column's reads and run as independent chains, the exponentials
+// go through exp4.  A product workgroup is often alone on its CU (one wave per SIMD, nothing to
+// hide a latency behind), where the entry-at-a-time form left every LDS read and every step of the
+// exp polynomial exposed.  Exact == 0 / == 1 fidelity masks (anything else: a zero row / column,
+// linear.py:67-70); r^2 in direct-difference form, il = [1 / lL | 1 / lD].
+template <int NB>
+__device__ __forceinline__ void post_mf_tile(double* Ks, const double* x1, const double* f1, const double* xs,
+                                             const double* fs, int D, const double* il, const double* th) {
+    constexpr int S = TileCfg<NB>::S;
+    constexpr int RSTEP = NTHREADS / NB;           // rows between a thread's consecutive entries
+    constexpr int NE = NB * NB / NTHREADS;         // entries per thread (a multiple of 4)
+    const int t = threadIdx.x, c = t % NB, rb = t / NB;
+    const double* xb = xs + c * PXS;
+    const double fb = fs[c];
+    const bool Lb = (fb == 0.0), Hb = (fb == 1.0);
+    const double vL = th[0], vD = th[1 + D], rho = th[2 + 2 * D];
+    for (int g = 0; g < NE; g += 4) {
+        const int r0 = rb + g * RSTEP;
+        const double* xa = x1 + r0 * PXS;
+        double kl[4] = {0.0, 0.0, 0.0, 0.0}, kd[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int d = 0; d < D; ++d) {
+            const double b = xb[d], lL = il[d], lD = il[PMAXD + d];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double df = xa[j * RSTEP * PXS + d] - b;
+                const double qL = df * lL, qD = df * lD;
+                kl[j] += qL * qL;
+                kd[j] += qD * qD;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { kl[j] *= -0.5; kd[j] *= -0.5; }
+        exp4(kl);
+        exp4(kd);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double fa = f1[r0 + j * RSTEP];
+            const bool La = (fa == 0.0), Ha = (fa == 1.0);
+            const double kL = vL * kl[j];
+            double v = (La && Lb) ? kL : (!(Ha && Hb) ? kL * rho : kL * (rho * rho) + vD * kd[j]);
+            if (!(La || Ha) || !(Lb || Hb)) v = 0.0;
+            Ks[(r0 + j * RSTEP) * S + c] = v;
+        }
+    }
+}
+
+// K_diag of one X* row (k_kdiag's expressions)
+__device__ __forceinline__ double post_kdiag(double f, const double* theta, int D, int nlf) {
+    if (nlf) {
+        const GraphTheta th{theta, D, nlf};
+        const int s = graph_source(f, nlf);
+        double v = 0.0;
+        if (s >= 0 && s < nlf) v = th.v(s);
+        else if (s == nlf) {
+            for (int k = 0; k < nlf; ++k) v += th.v(k) * (th.rho(k) * th.rho(k));
+            v += th.v(nlf);
+        }
+        return v;
+    }
+    const MFTheta th{theta, D};
+    const double rho = th.rho();
+    return (f == 0.0) ? th.vL() : ((f == 1.0) ? th.vL() * (rho * rho) + th.vD() : 0.0);
+}
+
+// sum over k < n of base[k * stride] in k order; the sc1 loads are issued eight at a time (one at a
+// time, a thread's sum cost a memory round trip per term)
+__device__ __forceinline__ double post_sum_coherent(const double* base, long stride, int n) {
+    double s = 0.0;
+    for (int k0 = 0; k0 < n; k0 += 8) {
+        double v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = k0 + j < n ? ld_coherent(base + (long)(k0 + j) * stride) : 0.0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s += v[j];
+    }
+    return s;
+}
+
+// the same for data of an earlier launch (plain loads)
+__device__ __forceinline__ double post_sum(const double* base, long stride, int n) {
+    double s = 0.0;
+    for (int k0 = 0; k0 < n; k0 += 8) {
+        double v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = k0 + j < n ? base[(long)(k0 + j) * stride] : 0.0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s += v[j];
+    }
+    return s;
+}
+
+template <int NB>
+constexpr size_t post_a_smem() {
+    return sizeof(double) * (3 * (size_t)TileCfg<NB>::ELEMS + 2 * NB * PXS + 2 * NB + 2 * PMAXD + PTHETA);
+}
+
+template <int NB>
+__global__ __launch_bounds__(NTHREADS) void k_post_a(PostArgs a) {
+    constexpr int S = TileCfg<NB>::S;
+    constexpr int E = TileCfg<NB>::ELEMS;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    double* Ls = smem;
+    double* Cs = Ls + E;
+    double* Ks = Cs + E;
+    double* x1 = Ks + E;            // NB x PXS: cached rows of the m-tile
+    double* xs = x1 + NB * PXS;     // NB x PXS: X* rows of the column tile
+    double* f1 = xs + NB * PXS;     // NB fidelity flags (-1: padding)
+    double* fs = f1 + NB;
+    double* il = fs + NB;           // [1 / lL | 1 / lD]
+    double* ths = il + 2 * PMAXD;   // theta
+    const int t = threadIdx.x, l = blockIdx.z;
+    const int task = blockIdx.x / a.Ts, cs = blockIdx.x % a.Ts;
+    if (blockIdx.x == 0 && l == 0)
+        for (int e = t; e < a.Ts; e += NTHREADS) a.cnt[e] = 0;   // k_post_out's arrival counters
+    // task -> (row tile i, chunk ch)
+    int i = 0, ch = task;
+    for (; i < a.T; ++i) {
+        const int nch = ((a.full ? a.T : i + 1) + a.chunk - 1) / a.chunk;
+        if (ch < nch) break;
+        ch -= nch;
+    }
+    if (i >= a.T) return;   // (never: the grid is post_ntasks x Ts)
+    const int m0 = ch * a.chunk;
+    const int mend = a.full ? a.T : i + 1;
+    const int m1 = m0 + a.chunk < mend ? m0 + a.chunk : mend;
+    const int D = a.D;
+    const double* tp = a.theta + l * a.stheta;
+    const int G = kernel_theta_size(a.nlf, D);
+    for (int e = t; e < G; e += NTHREADS) ths[e] = tp[e];
+    if (!a.nlf && t < D) {
+        il[t] = rcp_nr(tp[1 + t]);
+        il[PMAXD + t] = rcp_nr(tp[2 + D + t]);
+    }
+    for (int e = t; e < NB * D; e += NTHREADS) {
+        const int r = e / D, d = e % D, gs = cs * NB + r;
+        xs[r * PXS + d] = gs < a.nstar ? a.Xs[(long)gs * a.ldxs + d] : 0.0;
+    }
+    if (t < NB) {
+        const int gs = cs * NB + t;
+        fs[t] = gs < a.nstar ? a.Xs[(long)gs * a.ldxs + D] : -1.0;
+    }
+    const double* Li = a.Li + l * a.sL;
+    const double* Cm = a.C ? a.C + l * a.sC : nullptr;
+    const GraphTheta gth{ths, D, a.nlf};
+    Acc<NB> accA, accB;
+    acc_zero(accA);
+    acc_zero(accB);
+    // One memory round trip a step, hidden behind the previous step's tile generation and product:
+    // the next step's L^{-1} (C) tile, cached rows and flags are fetched into registers before the
+    // current step computes (a step that waited for its own loads took ~2x as long).
+    constexpr int PER = NB * PMAXD / NTHREADS;
+    TileRegs<NB> rl, rc;
+    double rx[PER], rf = -1.0;
+    auto fetch = [&](int m) {
+        if (m <= i) tile_fetch<NB>(rl, Li + (long)i * NB * a.ldl + (long)m * NB, a.ldl);
+        if (Cm) tile_fetch<NB>(rc, Cm + (long)i * NB * a.ldc + (long)m * NB, a.ldc);
+#pragma unroll
+        for (int q = 0; q < PER; ++q) {
+            const int e = t + q * NTHREADS;
+            rx[q] = 0.0;
+            if (e < NB * D) {
+                const int gr = m * NB + e / D;
+                if (gr < a.n1) rx[q] = a.X1[(long)gr * a.ldx1 + e % D];
+            }
+        }
+        if (t < NB) {
+            const int gr = m * NB + t;
+            rf = gr < a.n1 ? a.X1[(long)gr * a.ldx1 + D] : -1.0;
+        }
+    };
+    if (m0 < m1) fetch(m0);
+    for (int m = m0; m < m1; ++m) {
+        __syncthreads();   // the previous step's readers of x1 / Ls / Cs / Ks are done
+        if (m <= i) tile_put<NB>(Ls, rl);
+        if (Cm) tile_put<NB>(Cs, rc);
+#pragma unroll
+        for (int q = 0; q < PER; ++q) {
+            const int e = t + q * NTHREADS;
+            if (e < NB * D) x1[(e / D) * PXS + e % D] = rx[q];
+        }
+        if (t < NB) f1[t] = rf;
+        if (m + 1 < m1) fetch(m + 1);
+        __syncthreads();
+        if (a.nlf) {
+            for (int e = t; e < NB * NB; e += NTHREADS) {
+                const int r = e / NB, c = e % NB;
+                Ks[r * S + c] = graph_entry(x1 + r * PXS, xs + c * PXS, graph_source(f1[r], a.nlf),
+                                            graph_source(fs[c], a.nlf), gth);
+            }
+        } else {
+            post_mf_tile<NB>(Ks, x1, f1, xs, fs, D, il, ths);
+        }
+        __syncthreads();
+        if (m <= i) tile_mma<NB, false, false>(accA, Ls, Ks, 1.0);
+        if (Cm) tile_mma<NB, false, false>(accB, Cs, Ks, 1.0);
+    }
+    const long o = (((long)l * a.ntask + task) * a.Ts + cs) * (NB * NB);
+    acc_store(accA, a.Apart + o, NB);
+    if (Cm) acc_store(accB, a.Bpart + o, NB);
+}
+
+template <int NB>
+constexpr size_t post_out_smem() {
+    return sizeof(double) * 2 * post_rg(NB) * (size_t)TileCfg<NB>::ELEMS;
+}
+
+template <int NB>
+__global__ __launch_bounds__(NTHREADS) void k_post_out(PostArgs a) {
+    constexpr int S = TileCfg<NB>::S;
+    constexpr int E = TileCfg<NB>::ELEMS;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int RG = post_rg(NB);
+    double* As = smem;            // RG tiles: the group's A_i, kept across the output tiles
+    double* Bs = As + RG * E;     // RG tiles: the group's Z_i of one output tile (SVGP: the first holds B_i)
+    __shared__ int last;
+    const int t = threadIdx.x, l = blockIdx.z;
+    const int g = blockIdx.x / a.Ts, cs = blockIdx.x % a.Ts;
+    const int nspad = a.Ts * NB;
+    const int i0 = g * RG, i1 = i0 + RG < a.T ? i0 + RG : a.T;
+    double va = 0.0, vb = 0.0, pm = 0.0;   // thread c < NB: column c of the group's rows
+    for (int i = i0; i < i1; ++i) {
+        double* Ai = As + (i - i0) * E;
+        int base, nch;
+        post_row_tasks(a.T, a.chunk, a.full, i, base, nch);
+        // A_i (B_i) = the row's partials in task order
+        for (int e = t; e < NB * NB; e += NTHREADS) {
+            const int r = e / NB, c = e % NB;
+            const long o =(((long)l * a.ntask + base) * a.Ts + cs) * (NB * NB) + e;
+            const long st = (long)a.Ts * (NB * NB);
+            const double sa = post_sum(a.Apart + o, st, nch);
+            const double sb = a.C ? post_sum(a.Bpart + o, st, nch) : 0.0;
+            Ai[r * S + c] = sa;
+            if (a.C) Bs[r * S + c] = sb;
+            if (a.Am) a.Am[((long)i * NB + r) * a.ldam + cs * NB + c] = sa;
+        }
+        __syncthreads();
+        if (t < NB) {
+            const double* q = a.qmu ? a.qmu + (long)l * a.T * NB + (long)i * NB : nullptr;
+            for (int r = 0; r < NB; ++r) {
+                const double v = Ai[r * S + t];
+                va += v * v;
+                if (q) pm += v * q[r];
+                if (a.C) { const double w = Bs[r * S + t]; vb += w * w; }
+            }
+        }
+        __syncthreads();   // Bs is rewritten by the next row tile
+    }
+    if (t < NB) {
+        if (a.Zc) {
+            st_coherent(a.vpart + (long)g * nspad + cs * NB + t, va);
+        } else {
+            const long o = ((long)l * a.ngrp + g) * nspad + cs * NB + t;
+            st_coherent(a.pa + o, va);
+            st_coherent(a.pb + o, vb);
+            st_coherent(a.pm + o, pm);
+        }
+    }
+    const int ppad = a.Tp * NB;
+    if (a.Zc) {   // mean partial of the row group: sum_i A_i^T Z_i
+        for (int cy = 0; cy < a.Tp; ++cy) {
+            Acc<NB> acc;
+            acc_zero(acc);
+            __syncthreads();
+            for (int i = i0; i < i1; ++i)   // the group's Z tiles in one memory round trip
+                tile_load<NB>(Bs + (i - i0) * E, a.Zc + (long)i * NB * a.ldz + (long)cy * NB, a.ldz);
+            __syncthreads();
+            for (int i = i0; i < i1; ++i) tile_mma<NB, true, false>(acc, As + (i - i0) * E, Bs + (i - i0) * E, 1.0);
+            acc_store_coherent(acc, a.mpart + ((long)g * nspad + cs * NB) * ppad + cy * NB, ppad);
+        }
+    }
+    drain_stores();
+    __syncthreads();
+    if (t == 0) last = arrive(a.cnt + cs) == a.ngrp * (int)gridDim.z - 1;
+    __syncthreads();
+    if (!last) return;
+    // ---- the column tile's outputs, by its last workgroup (row partials in row order)
+    if (a.Zc) {
+        for (int e = t; e < NB * a.p; e += NTHREADS) {
+            const int r = e / a.p, c = e % a.p, s = cs * NB + r;
+            if (s >= a.nstar) break;
+            a.mean[(long)s * a.ldm + c] = post_sum_coherent(a.mpart + (long)s * ppad + c, (long)nspad * ppad, a.ngrp);
+        }
+        const int s = cs * NB + t;
+        if (t < NB && s < a.nstar) {
+            const double v = post_sum_coherent(a.vpart + s, nspad, a.ngrp);
+            a.var[s] = post_kdiag(a.Xs[(long)s * a.ldxs + a.D], a.theta, a.D, a.nlf) - v;
+        }
+        return;
+    }
+    const int L = (int)gridDim.z;
+    for (int e = t; e < L * NB; e += NTHREADS) {
+        const int ll = e / NB, s = cs * NB + e % NB;
+        if (s >= a.nstar) continue;
+        const long o = (long)ll * a.ngrp * nspad + s;
+        const double sa = post_sum_coherent(a.pa + o, nspad, a.ngrp);
+        const double sb = post_sum_coherent(a.pb + o, nspad, a.ngrp);
+        const double sm = post_sum_coherent(a.pm + o, nspad, a.ngrp);
+        const double kff = post_kdiag(a.Xs[(long)s * a.ldxs + a.D], a.theta + ll * a.stheta, a.D, 0);
+        st_coherent(a.gm + (long)ll * nspad + s, sm);
+        st_coherent(a.gv + (long)ll * nspad + s, kff - sa + sb);
+    }
+    drain_stores();
+    __syncthreads();
+    for (int e = t; e < NB * a.p; e += NTHREADS) {   // mixing f = g W^T, f_var = g_var (W o W)^T (k_svgp_mix)
+        const int r = e / a.p, c = e % a.p, s = cs * NB + r;
+        if (s >= a.nstar) break;
+        double fm = 0.0, fv = 0.0;
+        if (a.W) {
+            for (int l0 = 0; l0 < L; l0 += 8) {   // (the sc1 loads issued eight at a time, summed in latent order)
+                double gmv[8], gvv[8], w[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const bool in = l0 + j < L;
+                    gmv[j] = in ? ld_coherent(a.gm + (long)(l0 + j) * nspad + s) : 0.0;
+                    gvv[j] = in ? ld_coherent(a.gv + (long)(l0 + j) * nspad + s) : 0.0;
+                    w[j] = in ? a.W[(long)c * L + l0 + j] : 0.0;
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    fm += gmv[j] * w[j];
+                    fv += gvv[j] * (w[j] * w[j]);
+                }
+            }
+        } else {
+            fm = ld_coherent(a.gm + (long)c * nspad + s);
+            fv = ld_coherent(a.gv + (long)c * nspad + s);
+        }
+        a.f_mu[(long)s * a.p + c] = fm;
+        a.f_var[(long)s * a.p + c] = fv;
+    }
+}
+
+template <int NB>
+void launch_post(const PostArgs& a, int batch, hipStream_t s) {
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_post_a<NB>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)post_a_smem<NB>());
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_post_out<NB>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)post_out_smem<NB>());
+        attr = true;
+    }
+    hipLaunchKernelGGL(k_post_a<NB>, dim3(a.ntask * a.Ts, 1, batch), dim3(NTHREADS), post_a_smem<NB>(), s, a);
+    hipLaunchKernelGGL(k_post_out<NB>, dim3(a.ngrp * a.Ts, 1, batch), dim3(NTHREADS), post_out_smem<NB>(), s, a);
+}
+
+template void launch_post<32>(const PostArgs&, int, hipStream_t);
+template void launch_post<64>(const PostArgs&, int, hipStream_t);
+
+}  // namespace mfgp

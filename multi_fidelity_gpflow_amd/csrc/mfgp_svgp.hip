@@ -747,4 +747,74 @@ int svgp_predict_impl(hipStream_t s, int nb, int n, int m, int l, int p, int d, 
                         ws_bytes, nullptr, g_mu, g_var, info, f_mu, f_var);
 }
 
+// ---------------------------------------------------------------- cached posterior (mfgp_posterior.hip)
+// The X*-independent head of svgp_run for mfgp_svgp_posterior_build: Lm^{-1} (lower tiles, zeros
+// above) and C = Lq^T Lm^{-1} of every latent, written straight into the caller's cache blocks
+// ([l][Mpad][Mpad] each); Kuu, the factor's scratch and the padded tril(q_sqrt) live in ws.
+struct SvgpFactorLayout {
+    int Tm, mpad;
+    double *Kuu, *R, *Dd, *ldiag, *Lq;
+    size_t bytes;
+};
+static SvgpFactorLayout svgp_factor_layout(int nb, int m, int l, void* ws) {
+    SvgpFactorLayout S;
+    S.Tm = cdiv(m, nb);
+    S.mpad = S.Tm * nb;
+    const size_t mm = (size_t)S.mpad * S.mpad;
+    size_t off = 0;
+    char* base = (char*)ws;
+    auto take = [&](size_t count) {
+        off = (off + 255) & ~(size_t)255;
+        double* ptr = base ? reinterpret_cast<double*>(base + off) : nullptr;
+        off += count * sizeof(double);
+        return ptr;
+    };
+    S.Kuu = take(mm * l);
+    S.R = take(mm * l);
+    S.Dd = take((size_t)S.Tm * nb * nb * l);
+    S.ldiag = take((size_t)S.mpad * l);
+    S.Lq = take(mm * l);
+    S.bytes = off + 256;
+    return S;
+}
+size_t svgp_posterior_factor_bytes(int nb, int m, int l) { return svgp_factor_layout(nb, m, l, nullptr).bytes; }
+
+template <int NB>
+static int svgp_factor_run(hipStream_t s, int m, int L, int d, const double* Z, int ldz, const double* thetas,
+                           const double* q_sqrt, double jitter, void* ws, size_t ws_bytes, double* Li, double* C,
+                           int* info) {
+    const SvgpFactorLayout S = svgp_factor_layout(NB, m, L, ws);
+    if (ws_bytes < S.bytes) return -2;
+    const long mm = (long)S.mpad * S.mpad;
+    GramArgs g{};
+    g.X1 = Z; g.ldx1 = ldz; g.sx1 = 0; g.n1 = m;
+    g.X2 = Z; g.ldx2 = ldz; g.sx2 = 0; g.n2 = m;
+    g.theta = thetas; g.stheta = theta_size(d); g.D = d; g.rbf_only = 0;
+    g.out = S.Kuu; g.ldo = S.mpad; g.so = mm;
+    g.padded = 1; g.npad = S.mpad; g.tiles_c = S.Tm; g.add_noise = 0; g.diag_add = jitter;
+    g.R = NB == 32 ? nullptr : S.R; g.ldr = S.mpad; g.sR = mm;
+    launch_gram_dense(g, L, S.mpad, S.mpad, s);
+    launch_first_factor<NB>(S.Kuu, S.mpad, mm, S.Dd, (long)S.Tm * NB * NB, S.ldiag, S.mpad, info, L, s);
+    CholArgs c{};
+    c.A = S.Kuu; c.lda = S.mpad; c.sA = mm;
+    c.R = S.R; c.ldr = S.mpad; c.sR = mm;
+    c.Xo = Li; c.ldx = S.mpad; c.sX = mm;
+    c.Dd = S.Dd; c.sD = (long)S.Tm * NB * NB; c.ldiag = S.ldiag; c.sL = S.mpad; c.info = info;
+    c.T = S.Tm; c.Tp = 0; c.k = 0;
+    c.r_implicit = NB == 32 ? 1 : 0;
+    launch_chol_steps<NB>(c, L, s);
+    hipLaunchKernelGGL(k_zero_upper_tiles, dim3(cdiv(S.mpad, ZU_ROWS), 1, L), dim3(256), 0, s, Li, NB, S.mpad, mm);
+    hipLaunchKernelGGL(k_lq_pad, dim3(cdiv(S.mpad, ZU_ROWS), 1, L), dim3(256), 0, s, q_sqrt, m, S.mpad, S.Lq, 0);
+    hipLaunchKernelGGL(k_lqt_linv<NB>, dim3(S.Tm * S.Tm, 1, L), dim3(NTHREADS), 2 * sizeof(double) * NB * (NB + 2), s,
+                       S.Lq, Li, C, S.Tm);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int svgp_posterior_factor(hipStream_t s, int nb, int m, int l, int d, const double* Z, int ldz, const double* thetas,
+                          const double* q_sqrt, double jitter, void* ws, size_t ws_bytes, double* Li, double* C,
+                          int* info) {
+    if (nb == 64) return svgp_factor_run<64>(s, m, l, d, Z, ldz, thetas, q_sqrt, jitter, ws, ws_bytes, Li, C, info);
+    return svgp_factor_run<32>(s, m, l, d, Z, ldz, thetas, q_sqrt, jitter, ws, ws_bytes, Li, C, info);
+}
+
 }  // namespace mfgp

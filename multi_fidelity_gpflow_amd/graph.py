@@ -20,6 +20,7 @@ from .engine import Engine, to_dev
 from .kernels import GraphMultiFidelityKernel
 from ._lib import info_error
 from .models import Gaussian
+from .posteriors import GPRPosterior, PrecomputeCacheType
 from .params import (Module, Sigmoid, Softplus, as_result, gather_entries, scatter_entries, set_trainable,
                      tie_entries)
 from .session import _PackedAdam, _Session, check_outcome, span_from_tie
@@ -117,6 +118,11 @@ class GraphMultiFidelityGPModel(Module):
                                       "full_cov=False and full_output_cov=False")
         mean, var = self.predict_f(Xnew)
         return mean, as_result(var + float(self.likelihood.variance.numpy()))
+
+    def posterior(self, precompute_cache=PrecomputeCacheType.TENSOR):
+        """GPflow GPR.posterior(): a frozen snapshot of the parameters and data whose predict_f
+        reuses the precomputed inverse factor (posteriors.GPRPosterior)."""
+        return GPRPosterior(self, self.num_LF, self._theta, precompute_cache)
 
     # ------------------------------------------------------------ training
     def optimize(self, max_iters=1000, learning_rate=0.01, use_adam=True, unfix_noise_after=500, verbose=False,

@@ -31,6 +31,7 @@ from .engine import AdamState, Engine, resolve_dtype, theta_size, to_dev
 from .kernels import LinearMultiFidelityKernel
 from .params import (Module, Parameter, as_result, gather_entries, positive, scatter_entries, set_trainable,
                      tie_entries)
+from .posteriors import GPRPosterior, PrecomputeCacheType
 from .session import (CholeskyError, _Session, _StepRunner, _retire_graphs, _retired_graphs,  # noqa: F401
                       check_outcome, new_stream, release_retired_graphs)
 
@@ -227,6 +228,14 @@ class MultiFidelityGPModel(Module):
                                       "full_cov=False and full_output_cov=False")
         mean, var = self.predict_f(Xnew)
         return mean, as_result(var + float(self.likelihood.variance.numpy()))
+
+    def posterior(self, precompute_cache=PrecomputeCacheType.TENSOR):
+        """GPflow GPR.posterior(): a frozen snapshot of the parameters and data whose predict_f
+        reuses the precomputed inverse factor (posteriors.GPRPosterior).  fp64 only."""
+        if self.dtype != torch.float64:
+            raise NotImplementedError("posterior(): the float32 path is not cached yet; use predict_f, or a "
+                                      "float64 model")
+        return GPRPosterior(self, 0, lambda: self._theta_map().theta(), precompute_cache)
 
     # ------------------------------------------------------------ training
     def optimize(self, max_iters=1000, learning_rate=0.01, use_adam=True, unfix_noise_after=500, verbose=True,

@@ -1,0 +1,205 @@
+"""Cached posteriors: GPflow's ``model.posterior()`` for the four fp64 models.
+
+``model.posterior()`` freezes the model's parameters and training data and does the work of
+``predict_f`` that does not depend on ``Xnew`` once (include/mfgp.h ``mfgp_gpr_posterior_build`` /
+``mfgp_svgp_posterior_build``: Gram, factorization, inverse factor, projected targets).  The returned
+object's ``predict_f`` then runs only ``mfgp_*_posterior_predict`` against that device block: two
+launches, no Gram of X, no factorization, no parameter upload and no host read of a device word.
+
+The cache is a *snapshot*: assigning to the model or training it does not change what the cached
+``predict_f`` returns until ``update_cache()`` is called.  ``fused_predict_f`` never uses the cache:
+it is the model's own ``predict_f`` at the model's current parameters.
+"""
+from __future__ import annotations
+
+import enum
+
+import torch
+
+from ._lib import MFGPError, check, info_error, ptr
+from .engine import Engine, to_dev
+from .params import as_result
+from .session import CholeskyError
+
+
+class PrecomputeCacheType(enum.Enum):
+    """How a posterior keeps its precomputed quantities (the GPflow names).
+
+    TENSOR: ``update_cache()`` may allocate new device buffers.  VARIABLE: ``update_cache()``
+    rewrites the same device buffers (stable pointers, no reallocation while the shapes are
+    unchanged).  NOCACHE: nothing is precomputed and ``predict_f`` is ``fused_predict_f``."""
+    TENSOR = "tensor"
+    VARIABLE = "variable"
+    NOCACHE = "nocache"
+
+
+def _cache_type(value) -> PrecomputeCacheType:
+    if value is None:
+        return PrecomputeCacheType.NOCACHE
+    if isinstance(value, PrecomputeCacheType):
+        return value
+    return PrecomputeCacheType(str(value).lower())
+
+
+class _Posterior:
+    """Shared surface: predict_f / fused_predict_f / update_cache and the cache buffer policy."""
+
+    def __init__(self, model, precompute_cache):
+        self.model = model
+        self._precompute_cache = None
+        self.cache = None        # the device block (uint8 tensor), None without a cache
+        self._valid = False
+        self.update_cache(_cache_type(precompute_cache))
+
+    def fused_predict_f(self, Xnew, full_cov: bool = False, full_output_cov: bool = False):
+        """The model's own predict_f at the model's CURRENT parameters (never the cache)."""
+        return self.model.predict_f(Xnew, full_cov=full_cov, full_output_cov=full_output_cov)
+
+    def update_cache(self, precompute_cache=None):
+        """Re-snapshot the model's parameters and data (None: keep the cache type).  A failed
+        factorization raises CholeskyError here; a VARIABLE cache is then unusable until an
+        update succeeds, a TENSOR one keeps its previous contents."""
+        if precompute_cache is not None:
+            self._precompute_cache = _cache_type(precompute_cache)
+        if self._precompute_cache is PrecomputeCacheType.NOCACHE:
+            self.cache, self._valid = None, False
+            return
+        self._build()
+
+    def _cache_buffer(self, eng: Engine, nbytes: int) -> torch.Tensor:
+        """VARIABLE: the existing block while it is large enough; otherwise a new one."""
+        if (self._precompute_cache is PrecomputeCacheType.VARIABLE and self.cache is not None
+                and self.cache.numel() >= nbytes and self.cache.device == eng.device):
+            return self.cache
+        return torch.empty(int(nbytes), dtype=torch.uint8, device=eng.device)
+
+    def _commit(self, buf: torch.Tensor, info: torch.Tensor, what: str):
+        """Build-time check of the factorization (the only host read of info): raise, or adopt buf."""
+        bad = int(info.max().item()) if info.numel() > 1 else int(info.reshape(-1)[0].item())
+        if bad != 0:
+            if buf is self.cache:
+                self._valid = False
+            if info.numel() > 1:
+                raise CholeskyError(f"{what}: Cholesky of K_uu was not successful")
+            raise info_error(bad, what)
+        self.cache, self._valid = buf, True
+
+    def _require_cache(self, eng: Engine):
+        if not self._valid:
+            raise MFGPError("posterior: the cache is not valid (its last update failed); call update_cache()")
+        if eng.tile() != self._nb:
+            raise MFGPError(f"posterior: the cache was built for tile size {self._nb}, the engine now runs "
+                            f"{eng.tile()}; call update_cache()")
+
+
+class GPRPosterior(_Posterior):
+    """Posterior of MultiFidelityGPModel (nlf = 0) / GraphMultiFidelityGPModel (nlf = its LF sources).
+
+    The cache holds X, theta, L^{-1} and Z = L^{-1} Y; ``predict_f`` (marginal and ``full_cov=True``)
+    is computed from it alone: A = L^{-1} K(X, X*) with K generated inside the product kernel,
+    mean = A^T Z, var = K_diag(X*) - colsum(A^2), cov = K(X*, X*) - A^T A."""
+
+    def __init__(self, model, nlf: int, theta_fn, precompute_cache):
+        self._nlf = int(nlf)
+        self._theta_fn = theta_fn
+        super().__init__(model, precompute_cache)
+
+    def _build(self):
+        eng, X, Y = self.model._device_data()
+        theta = torch.tensor(self._theta_fn(), dtype=torch.float64, device=eng.device)
+        n, dp1 = X.shape
+        p, d, nlf = Y.shape[1], dp1 - 1, self._nlf
+        lib = eng.lib
+        nbytes = eng._size(lib.mfgp_gpr_posterior_size, nlf, n, p, d)
+        ws = eng.workspace("pred_cov", eng._size(lib.mfgp_gpr_predict_cov_workspace_size, nlf, n, p, d, 1))
+        buf = self._cache_buffer(eng, nbytes)
+        info = torch.empty((1,), dtype=torch.int32, device=eng.device)
+        check(lib.mfgp_gpr_posterior_build(eng.h, nlf, n, p, d, ptr(X), dp1, ptr(Y), p, ptr(theta), ptr(ws),
+                                           ws.numel(), ptr(buf), buf.numel(), ptr(info)), "mfgp_gpr_posterior_build")
+        self._shape, self._nb = (n, p, d), eng.tile()
+        self._commit(buf, info, "posterior")
+
+    def predict_f(self, Xnew, full_cov: bool = False, full_output_cov: bool = False):
+        """The model's predict_f at the snapshot (same shapes: mean [N*, P]; var [N*, P] or, with
+        full_cov, [P, N*, N*]).  Uploads Xnew when it is not a device tensor, enqueues, returns."""
+        if full_output_cov:
+            raise NotImplementedError("predict_f(full_output_cov=True): GPR has no output covariance to return")
+        if self._precompute_cache is PrecomputeCacheType.NOCACHE:
+            return self.fused_predict_f(Xnew, full_cov=full_cov)
+        eng = Engine.get(self.cache.device if self.cache is not None else None)
+        self._require_cache(eng)
+        n, p, d = self._shape
+        Xs = to_dev(Xnew, eng.device)
+        ns = Xs.shape[0]
+        f64 = dict(dtype=torch.float64, device=eng.device)
+        mean, var = torch.empty((ns, p), **f64), torch.empty((ns,), **f64)
+        cov = torch.empty((ns, ns), **f64) if full_cov else None
+        if ns:
+            lib = eng.lib
+            ws = eng.workspace("post_pred", eng._size(lib.mfgp_gpr_posterior_predict_workspace_size, self._nlf, n, p,
+                                                      d, ns))
+            check(lib.mfgp_gpr_posterior_predict(eng.h, self._nlf, n, p, d, ns, ptr(self.cache), self.cache.numel(),
+                                                 ptr(Xs), Xs.shape[1], ptr(ws), ws.numel(), ptr(mean), p, ptr(var),
+                                                 ptr(cov), ns), "mfgp_gpr_posterior_predict")
+        if full_cov:
+            return as_result(mean), as_result(cov[None].expand(p, -1, -1).contiguous())
+        return as_result(mean), as_result(var[:, None].expand(-1, p).contiguous())
+
+
+class SVGPPosterior(_Posterior):
+    """Posterior of SingleBinSVGP / LatentMFCoregionalizationSVGP (any likelihood: it does not enter
+    predict_f).
+
+    The cache holds Z, the per-latent kernel parameters, W, q_mu, Lm^{-1} and Lq^T Lm^{-1}; the
+    marginal ``predict_f`` is computed from it alone.  The covariance forms (``full_cov`` /
+    ``full_output_cov``) are NOT cached: they run the model's covariance entry point
+    (mfgp_svgp_predict_cov, factorization included) on the snapshot's parameters, which keeps the
+    snapshot semantics."""
+
+    def __init__(self, model, jitter: float, precompute_cache):
+        self._jitter = float(jitter)
+        self._state = None
+        super().__init__(model, precompute_cache)
+
+    def _build(self):
+        eng, Z, thetas, q_mu, q_sqrt, W = self.model._dev_state()
+        m, dp1 = Z.shape
+        d, L, p = dp1 - 1, thetas.shape[0], int(self.model.num_outputs)
+        lib = eng.lib
+        nbytes = eng._size(lib.mfgp_svgp_posterior_size, m, L, p, d)
+        ws = eng.workspace("svgp_pred", eng._size(lib.mfgp_svgp_workspace_size, 1, m, L, p, d))
+        buf = self._cache_buffer(eng, nbytes)
+        info = torch.empty((L,), dtype=torch.int32, device=eng.device)
+        check(lib.mfgp_svgp_posterior_build(eng.h, m, L, p, d, ptr(Z), dp1, ptr(thetas), ptr(q_mu), ptr(q_sqrt),
+                                            ptr(W), self._jitter, ptr(ws), ws.numel(), ptr(buf), buf.numel(),
+                                            ptr(info)), "mfgp_svgp_posterior_build")
+        self._shape, self._nb = (m, L, p, d, W is not None), eng.tile()
+        self._state = (Z, thetas, q_mu, q_sqrt, W)   # the snapshot the covariance forms run on
+        self._commit(buf, info, "posterior")
+
+    def predict_f(self, Xnew, full_cov: bool = False, full_output_cov: bool = False):
+        """The model's predict_f at the snapshot: mean [N*, P]; var [N*, P], or the model's
+        covariance forms (not cached, see the class docstring)."""
+        if self._precompute_cache is PrecomputeCacheType.NOCACHE:
+            return self.fused_predict_f(Xnew, full_cov=full_cov, full_output_cov=full_output_cov)
+        eng = Engine.get(self.cache.device if self.cache is not None else None)
+        self._require_cache(eng)
+        m, L, p, d, mixed = self._shape
+        Xs = to_dev(Xnew, eng.device)
+        if full_cov or full_output_cov:
+            mode = 3 if (full_cov and full_output_cov) else (1 if full_cov else 2)
+            Z, thetas, q_mu, q_sqrt, W = self._state
+            f_mu, f_cov, info = eng.svgp_predict_cov(mode, Xs, Z, thetas, q_mu, q_sqrt, W, p, self._jitter)
+            if int(info.max().item()) != 0:
+                raise CholeskyError("predict_f: Cholesky of K_uu was not successful")
+            return as_result(f_mu), as_result(f_cov)
+        ns = Xs.shape[0]
+        f64 = dict(dtype=torch.float64, device=eng.device)
+        f_mu, f_var = torch.empty((ns, p), **f64), torch.empty((ns, p), **f64)
+        if ns:
+            lib = eng.lib
+            ws = eng.workspace("post_pred", eng._size(lib.mfgp_svgp_posterior_predict_workspace_size, ns, m, L, p, d))
+            check(lib.mfgp_svgp_posterior_predict(eng.h, ns, m, L, p, d, 1 if mixed else 0, ptr(self.cache),
+                                                  self.cache.numel(), ptr(Xs), Xs.shape[1], ptr(ws), ws.numel(),
+                                                  ptr(f_mu), ptr(f_var)), "mfgp_svgp_posterior_predict")
+        return as_result(f_mu), as_result(f_var)

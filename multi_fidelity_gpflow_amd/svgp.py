@@ -28,6 +28,7 @@ import torch
 from .engine import Engine, theta_size, to_dev
 from .kernels import LinearCoregionalization, LinearMultiFidelityKernel, SeparateIndependent
 from .models import CholeskyError, Gaussian, HeteroscedasticGaussian, MaskedGaussian
+from .posteriors import PrecomputeCacheType, SVGPPosterior
 from .params import (Module, Parameter, Softplus, as_result, gather_entries, multiple_assign, parameter_dict,
                      scatter_entries, tie_entries)
 from .session import _PackedAdam, _Session, check_outcome, span_from_tie
@@ -199,6 +200,11 @@ class _SVGPBase(Module):
         if self._masked():
             return mean, as_result(var + to_dev(self._noise_vector(), var.device)[None, :])
         return mean, as_result(var + self._noise())
+
+    def posterior(self, precompute_cache=PrecomputeCacheType.TENSOR):
+        """GPflow SVGP.posterior(): a frozen snapshot of Z, the kernels, q(u) and W whose marginal
+        predict_f reuses the precomputed K_uu factors (posteriors.SVGPPosterior)."""
+        return SVGPPosterior(self, DEFAULT_JITTER, precompute_cache)
 
     def elbo_and_grad(self, data, kl_multiplier=1.0):
         """(ELBO, dict of d(VE*scale - kl_multiplier*KL)/d(constrained parameter)) on the device:
