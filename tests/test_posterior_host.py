@@ -90,6 +90,67 @@ def test_svgp_posterior_sizes(lib, h):
     assert lib.mfgp_svgp_posterior_predict_workspace_size(h, 1, m, L, p, d, None) == -1
 
 
+def _ntasks(T, chunk, full):
+    """post_ntasks (mfgp_posterior.hip): row tile i has ceil((full ? T : i + 1) / chunk) tasks."""
+    return sum(-(-(T if full else i + 1) // chunk) for i in range(T))
+
+
+# (n or M, p, d, batch, svgp, nstar, whole rows?) of tests/test_gpu_posterior.py's schedule cases (NB = 32)
+SCHEDULE_CASES = {
+    "gpr-whole-rows-n500-ns512": (500, 3, 3, 1, False, 512, True),
+    "gpr-chunked-n500-ns32": (500, 3, 3, 1, False, 32, False),
+    "gpr-9-partials-n2081-ns33": (2081, 2, 1, 1, False, 33, False),
+    "gpr-9-partials-n2081-ns1": (2081, 2, 1, 1, False, 1, False),
+    "svgp-chunked-m270-l3-ns1": (270, 6, 5, 3, True, 1, False),
+    "svgp-chunked-m270-l3-ns33": (270, 6, 5, 3, True, 33, False),
+    "svgp-whole-rows-m270-l3-ns320": (270, 6, 5, 3, True, 320, True),
+}
+
+
+@pytest.mark.parametrize("case", list(SCHEDULE_CASES))
+def test_posterior_shapes_reach_their_schedule(case, lib, h):
+    """Which k_post_a schedule a shape takes (whole rows, or 8-tile chunks: post_chunk switches at
+    batch T Ts >= 256) cannot be seen from a prediction, but it sets the workspace size: Apart (and
+    Bpart for SVGP) is batch x ntask x Ts x nb^2 doubles.  The reported size must be the intended
+    schedule's partials plus the other post_layout buffers (restated here, each aligned to 256 B), and the
+    other schedule's partials plus the same buffers must not fit that size.  If this fails, the 256
+    threshold or POST_CHUNK moved: revisit the shapes of tests/test_gpu_posterior.py's schedule tests,
+    which then no longer run the paths they name."""
+    nm, p, d, batch, svgp, nstar, whole = SCHEDULE_CASES[case]
+    nb = 32
+    T, Tp, Ts = -(-nm // nb), -(-p // nb), -(-nstar // nb)
+    nspad, ngrp = Ts * nb, -(-T // 4)
+    assert (batch * T * Ts >= 256) == whole, "the case is on the wrong side of the whole-row threshold"
+    want, other = (T, 8) if whole else (8, T)
+    nt_want, nt_other = _ntasks(T, want, svgp), _ntasks(T, other, svgp)
+    assert nt_want != nt_other, "the two schedules cut this shape alike: the case tells nothing"
+    if not whole and not svgp:
+        assert T > 8
+    if case.startswith("gpr-9-partials"):
+        assert -(-T // 8) == 9            # the last row tile: more than post_sum's 8 loads at a time
+    if svgp and not whole:
+        assert T > 8                      # tasks wholly right of the diagonal, and nch > 1 partials
+    sz = C.c_size_t()
+    if svgp:
+        assert lib.mfgp_svgp_posterior_predict_workspace_size(h, nstar, nm, batch, p, d, C.byref(sz)) == 0
+        rest = [4 * Ts] + [8 * batch * ngrp * nspad] * 3 + [8 * batch * nspad] * 2
+        nparts = 2
+    else:
+        assert lib.mfgp_gpr_posterior_predict_workspace_size(h, 0, nm, p, d, nstar, C.byref(sz)) == 0
+        rest = [4 * Ts, 8 * ngrp * nspad * Tp * nb, 8 * ngrp * nspad, 8 * T * nb * nspad, 8 * nspad * nspad,
+                8 * nspad * nspad]
+        nparts = 1
+    part = lambda ntask: nparts * 8 * batch * ntask * Ts * nb * nb
+    slack = 256 * (len(rest) + nparts + 1)            # the carve's alignment and its closing 256 B
+    lo = part(nt_want) + sum(rest)
+    print(f"{case}: {sz.value} B, partials {part(nt_want)} B ({nt_want} tasks; the other schedule: {nt_other})")
+    assert part(nt_want) <= sz.value <= lo + slack
+    assert lo <= sz.value
+    lo_other = part(nt_other) + sum(rest)
+    assert not (lo_other <= sz.value <= lo_other + slack)
+    assert abs(part(nt_other) - part(nt_want)) > slack
+
+
 def test_posterior_calls_validate_before_device_work(lib, h):
     """Null pointers: -1.  A cache or workspace below the reported size: MFGP_ERR_WORKSPACE (-2).  The
     pointers are never dereferenced on these paths (there is no device here to take them)."""
