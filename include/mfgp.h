@@ -402,6 +402,30 @@ int mfgp_svgp_posterior_predict(mfgp_handle_t h, int nstar, int m, int l, int p,
                                 size_t cache_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes,
                                 double* f_mu, double* f_var);
 
+/* Input gradients of the cached predict calls: the vector-Jacobian product w.r.t. Xs.
+ * Arguments as the predict calls (GPR: no cov), plus the upstream gradients gmean [nstar x p]
+ * (ldgm) and gvar (GPR: [nstar], the derivative w.r.t. var; SVGP: [nstar x p] dense) -- either may be
+ * NULL, meaning zero -- and the output gX [nstar x (d + 1)] (ldgx):
+ *   gX[s][k] = sum_c gmean[s][c] dmean[s][c] / dXs[s][k] + (sum_c) gvar[s][(c)] dvar[s][(c)] / dXs[s][k].
+ * The fidelity column of Xs enters only through exact == 0 / == 1 tests: gX[s][d] = 0.  mean / var
+ * (f_mu / f_var) are written by the predict calls' own forward code (the same bits).  One more
+ * launch behind the predict call's two; no floating-point atomics, so two calls with the same
+ * inputs return the same bits.  Workspace: the *_vjp_workspace_size calls (MFGP_ERR_WORKSPACE
+ * before any device work when smaller); nothing is allocated, no device word is read by the host;
+ * nstar = 0 is a no-op.  The graph kernel (nlf > 0) is not supported: MFGP_ERR_ARG. */
+int mfgp_gpr_posterior_predict_vjp_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar,
+                                                  size_t* bytes);
+int mfgp_gpr_posterior_predict_vjp(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar, const void* cache,
+                                   size_t cache_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes,
+                                   double* mean, int ldm, double* var, const double* gmean, int ldgm,
+                                   const double* gvar, double* gX, int ldgx);
+int mfgp_svgp_posterior_predict_vjp_workspace_size(mfgp_handle_t h, int nstar, int m, int l, int p, int d,
+                                                   size_t* bytes);
+int mfgp_svgp_posterior_predict_vjp(mfgp_handle_t h, int nstar, int m, int l, int p, int d, int mixed,
+                                    const void* cache, size_t cache_bytes, const double* Xs, int ldxs, void* ws,
+                                    size_t ws_bytes, double* f_mu, double* f_var, const double* gmean, int ldgm,
+                                    const double* gvar, double* gX, int ldgx);
+
 /* Diagnostic: one v_mfma_f64_16x16x4_f64 with A[i][k] = 4i+k+1, B[k][j] = 100k+j;
  * writes C (16x16 row-major, device). */
 int mfgp_selftest_mfma(mfgp_handle_t h, double* out);

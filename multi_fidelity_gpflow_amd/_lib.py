@@ -94,6 +94,12 @@ SIGNATURES = {
     "mfgp_svgp_posterior_build": [_p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _d, _p, _sz, _p, _sz, _p],
     "mfgp_svgp_posterior_predict_workspace_size": [_p, _i, _i, _i, _i, _i, C.POINTER(_sz)],
     "mfgp_svgp_posterior_predict": [_p, _i, _i, _i, _i, _i, _i, _p, _sz, _p, _i, _p, _sz, _p, _p],
+    "mfgp_gpr_posterior_predict_vjp_workspace_size": [_p, _i, _i, _i, _i, _i, C.POINTER(_sz)],
+    "mfgp_gpr_posterior_predict_vjp": [_p, _i, _i, _i, _i, _i, _p, _sz, _p, _i, _p, _sz, _p, _i, _p, _p, _i, _p, _p,
+                                       _i],
+    "mfgp_svgp_posterior_predict_vjp_workspace_size": [_p, _i, _i, _i, _i, _i, C.POINTER(_sz)],
+    "mfgp_svgp_posterior_predict_vjp": [_p, _i, _i, _i, _i, _i, _i, _p, _sz, _p, _i, _p, _sz, _p, _p, _p, _i, _p, _p,
+                                        _i],
     "mfgp_selftest_mfma": [_p, _p],
     # dtype-generic forms (MFGP_F64 = 0, MFGP_F32 = 1)
     "mfgp_set_f32_panel": [_p, _i],

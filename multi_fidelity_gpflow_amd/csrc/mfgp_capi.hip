@@ -880,6 +880,33 @@ static PostLayout post_layout(int nb, int T, int Tp, int nstar, int batch, bool 
     return P;
 }
 
+// The VJP calls' workspace: the predict layout, then the input-gradient partials, k_post_grad's
+// counters and (SVGP) the kept A / B of every latent.
+struct PostGradIO {
+    const double* gmean; long ldgm;
+    const double* gvar;
+    double* gX; long ldgx;
+};
+struct PostGradLayout {
+    double *gpart, *glat, *Am, *Bm;
+    int* gcnt;
+    size_t bytes;
+};
+static PostGradLayout post_grad_layout(int nb, const PostLayout& P, int T, int d, int batch, bool svgp, void* ws) {
+    PostGradLayout G{};
+    const size_t o = (P.bytes + 255) & ~(size_t)255;
+    Carve c(ws ? (char*)ws + o : nullptr);
+    G.gpart = c.take<double>((size_t)batch * P.ntask * P.Ts * nb * (d > 0 ? d : 1));
+    G.gcnt = c.take<int>((size_t)P.Ts * (1 + batch));
+    if (svgp) {
+        G.glat = c.take<double>((size_t)batch * P.Ts * nb * (d > 0 ? d : 1));
+        G.Am = c.take<double>((size_t)batch * T * nb * P.nspad);
+        G.Bm = c.take<double>((size_t)batch * T * nb * P.nspad);
+    }
+    G.bytes = o + c.off + 256;
+    return G;
+}
+
 template <int NB>
 static int gpr_posterior_build_impl(mfgp_handle_t h, int nlf, int n, int p, int d, const double* X, int ldx,
                                     const double* Y, int ldy, const double* theta, void* ws, size_t ws_bytes,
@@ -903,10 +930,12 @@ static int gpr_posterior_build_impl(mfgp_handle_t h, int nlf, int n, int p, int 
 template <int NB>
 static int gpr_posterior_predict_impl(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar, const void* cache,
                                       size_t cache_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes,
-                                      double* mean, int ldm, double* var, double* cov, int ldc) {
+                                      double* mean, int ldm, double* var, double* cov, int ldc,
+                                      const PostGradIO* g = nullptr) {
     const GprCache c = gpr_cache_layout(NB, nlf, n, p, d, const_cast<void*>(cache));
     const PostLayout P = post_layout(NB, c.T, c.Tp, nstar, 1, false, ws);
-    if (cache_bytes < c.bytes || ws_bytes < P.bytes) return MFGP_ERR_WORKSPACE;
+    const PostGradLayout G = post_grad_layout(NB, P, c.T, d, 1, false, ws);
+    if (cache_bytes < c.bytes || ws_bytes < (g ? G.bytes : P.bytes)) return MFGP_ERR_WORKSPACE;
     hipStream_t s = h->stream;
     PostArgs a{};
     a.Li = c.LZ; a.ldl = c.ldr; a.sL = 0;
@@ -917,10 +946,16 @@ static int gpr_posterior_predict_impl(mfgp_handle_t h, int nlf, int n, int p, in
     a.T = c.T; a.Ts = P.Ts; a.chunk = P.chunk; a.full = 0; a.ntask = P.ntask; a.ngrp = P.ngrp;
     a.Apart = P.Apart; a.cnt = P.cnt;
     a.Zc = c.LZ + c.npad; a.ldz = c.ldr; a.Tp = c.Tp; a.p = p;
-    a.Am = cov ? P.Am : nullptr; a.ldam = P.nspad;
+    a.Am = (cov || g) ? P.Am : nullptr; a.ldam = P.nspad;
     a.mpart = P.mpart; a.vpart = P.vpart;
     a.mean = mean; a.ldm = ldm; a.var = var;
+    if (g) {
+        a.gmean = g->gmean; a.ldgm = g->ldgm; a.gvar = g->gvar;
+        a.gpart = G.gpart; a.glat = G.glat; a.gcnt = G.gcnt;
+        a.gX = g->gX; a.ldgx = g->ldgx;
+    }
     launch_post<NB>(a, 1, s);
+    if (g) launch_post_grad<NB>(a, 1, s);
     if (cov) {
         // base_conditional(full_cov=True): Kss - A^T A, as the tail of predict_impl (theta from the cache)
         if (nlf) (void)hipMemsetAsync(P.Kss, 0, sizeof(double) * (size_t)P.nspad * P.nspad, s);
@@ -1006,10 +1041,12 @@ static int svgp_posterior_build_impl(mfgp_handle_t h, int m, int l, int p, int d
 
 static int svgp_posterior_predict_impl(mfgp_handle_t h, int nstar, int m, int l, int p, int d, int mixed,
                                        const void* cache, size_t cache_bytes, const double* Xs, int ldxs, void* ws,
-                                       size_t ws_bytes, double* f_mu, double* f_var) {
+                                       size_t ws_bytes, double* f_mu, double* f_var,
+                                       const PostGradIO* g = nullptr) {
     const SvgpCache c = svgp_cache_layout(h->nb, m, l, p, d, const_cast<void*>(cache));
     const PostLayout P = post_layout(h->nb, c.Tm, 0, nstar, l, true, ws);
-    if (cache_bytes < c.bytes || ws_bytes < P.bytes) return MFGP_ERR_WORKSPACE;
+    const PostGradLayout G = post_grad_layout(h->nb, P, c.Tm, d, l, true, ws);
+    if (cache_bytes < c.bytes || ws_bytes < (g ? G.bytes : P.bytes)) return MFGP_ERR_WORKSPACE;
     const long mm = (long)c.mpad * c.mpad;
     PostArgs a{};
     a.Li = c.Li; a.ldl = c.mpad; a.sL = mm;
@@ -1024,8 +1061,18 @@ static int svgp_posterior_predict_impl(mfgp_handle_t h, int nstar, int m, int l,
     a.qmu = c.qmu; a.pa = P.pa; a.pb = P.pb; a.pm = P.pm; a.gm = P.gm; a.gv = P.gv;
     a.W = mixed ? c.W : nullptr;
     a.f_mu = f_mu; a.f_var = f_var;
+    if (g) {
+        a.Am = G.Am; a.Bm = G.Bm; a.ldam = P.nspad; a.sAm = (long)c.mpad * P.nspad;
+        a.gmean = g->gmean; a.ldgm = g->ldgm; a.gvar = g->gvar;
+        a.gpart = G.gpart; a.glat = G.glat; a.gcnt = G.gcnt;
+        a.gX = g->gX; a.ldgx = g->ldgx;
+    }
     if (h->nb == 64) launch_post<64>(a, l, h->stream);
     else launch_post<32>(a, l, h->stream);
+    if (g) {
+        if (h->nb == 64) launch_post_grad<64>(a, l, h->stream);
+        else launch_post_grad<32>(a, l, h->stream);
+    }
     return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
 }
 
@@ -1716,6 +1763,37 @@ int mfgp_gpr_posterior_predict(mfgp_handle_t h, int nlf, int n, int p, int d, in
                                           ldm, var, cov, ldc);
 }
 
+int mfgp_gpr_posterior_predict_vjp_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar,
+                                                  size_t* bytes) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nlf != 0 || n < 1 || p < 1 || nstar < 1 || !bytes) return MFGP_ERR_ARG;
+    const GprCache c = gpr_cache_layout(h->nb, nlf, n, p, d, nullptr);
+    const PostLayout P = post_layout(h->nb, c.T, c.Tp, nstar, 1, false, nullptr);
+    *bytes = post_grad_layout(h->nb, P, c.T, d, 1, false, nullptr).bytes;
+    return MFGP_OK;
+}
+
+int mfgp_gpr_posterior_predict_vjp(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar, const void* cache,
+                                   size_t cache_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes,
+                                   double* mean, int ldm, double* var, const double* gmean, int ldgm,
+                                   const double* gvar, double* gX, int ldgx) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nlf != 0) return MFGP_ERR_ARG;   // the graph kernel's per-source derivative is not built
+    if (nstar == 0) return MFGP_OK;
+    if (n < 1 || p < 1 || nstar < 0 || !cache || !Xs || !ws || !mean || !var || !gX || ldxs < d + 1 || ldm < p ||
+        ldgx < d + 1)
+        return MFGP_ERR_ARG;
+    if (gmean && ldgm < p) return MFGP_ERR_ARG;
+    const PostGradIO g{gmean, ldgm, gvar, gX, ldgx};
+    if (h->nb == 64)
+        return gpr_posterior_predict_impl<64>(h, nlf, n, p, d, nstar, cache, cache_bytes, Xs, ldxs, ws, ws_bytes, mean,
+                                              ldm, var, nullptr, 0, &g);
+    return gpr_posterior_predict_impl<32>(h, nlf, n, p, d, nstar, cache, cache_bytes, Xs, ldxs, ws, ws_bytes, mean,
+                                          ldm, var, nullptr, 0, &g);
+}
+
 int mfgp_svgp_posterior_size(mfgp_handle_t h, int m, int l, int p, int d, size_t* bytes) {
     CHECK_H(h);
     CHECK_D(d);
@@ -1754,6 +1832,34 @@ int mfgp_svgp_posterior_predict(mfgp_handle_t h, int nstar, int m, int l, int p,
     if (!mixed && l != p) return MFGP_ERR_ARG;
     return svgp_posterior_predict_impl(h, nstar, m, l, p, d, mixed, cache, cache_bytes, Xs, ldxs, ws, ws_bytes, f_mu,
                                        f_var);
+}
+
+int mfgp_svgp_posterior_predict_vjp_workspace_size(mfgp_handle_t h, int nstar, int m, int l, int p, int d,
+                                                   size_t* bytes) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nstar < 1 || m < 1 || l < 1 || p < 1 || !bytes) return MFGP_ERR_ARG;
+    const int T = ceil_div(m, h->nb);
+    const PostLayout P = post_layout(h->nb, T, 0, nstar, l, true, nullptr);
+    *bytes = post_grad_layout(h->nb, P, T, d, l, true, nullptr).bytes;
+    return MFGP_OK;
+}
+
+int mfgp_svgp_posterior_predict_vjp(mfgp_handle_t h, int nstar, int m, int l, int p, int d, int mixed,
+                                    const void* cache, size_t cache_bytes, const double* Xs, int ldxs, void* ws,
+                                    size_t ws_bytes, double* f_mu, double* f_var, const double* gmean, int ldgm,
+                                    const double* gvar, double* gX, int ldgx) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nstar == 0) return MFGP_OK;
+    if (nstar < 0 || m < 1 || l < 1 || p < 1 || !cache || !Xs || !ws || !f_mu || !f_var || !gX || ldxs < d + 1 ||
+        ldgx < d + 1)
+        return MFGP_ERR_ARG;
+    if (!mixed && l != p) return MFGP_ERR_ARG;
+    if (gmean && ldgm < p) return MFGP_ERR_ARG;
+    const PostGradIO g{gmean, ldgm, gvar, gX, ldgx};
+    return svgp_posterior_predict_impl(h, nstar, m, l, p, d, mixed, cache, cache_bytes, Xs, ldxs, ws, ws_bytes, f_mu,
+                                       f_var, &g);
 }
 
 int mfgp_selftest_mfma(mfgp_handle_t h, double* out) {

@@ -197,12 +197,25 @@ struct PostArgs {
     double *gm, *gv;                          // [batch][Nspad] latent moments
     const double* W;                          // mixing [p][batch]; nullptr: identity (batch == p)
     double* f_mu; double* f_var;              // [nstar][p]
+    // Input-gradient pass (k_post_grad, behind the two forward launches; all unset for a plain predict).
+    // GPR keeps A in Am; SVGP keeps A and B per batch entry (stride sAm, rows as Am).
+    long sAm; double* Bm;
+    const double* gmean; long ldgm;           // upstream d / d mean [nstar x p]; nullptr: zero
+    const double* gvar;                       // upstream d / d var: GPR [nstar], SVGP [nstar x p]; nullptr: zero
+    double* gpart;                            // [batch][ntask][Ts][D][NB] partial input gradients
+    double* glat;                             // [batch][Ts][D][NB] per batch entry sums (batch > 1)
+    int* gcnt;                                // k_post_grad's arrival counters: [Ts], then [batch][Ts] (zeroed by k_post_a)
+    double* gX; long ldgx;                    // [nstar x (D + 1)], fidelity column written as 0
 };
 // tasks of one batch entry: row tile i has ceil((full ? T : i + 1) / chunk) of them
 int post_ntasks(int T, int chunk, int full);
 // row tiles one k_post_out workgroup takes (128 rows: its A tiles stay in LDS across the output tiles)
 constexpr int post_rg(int nb) { return nb == 32 ? 4 : 2; }
 template <int NB> void launch_post(const PostArgs& a, int batch, hipStream_t s);
+// The VJP of the predict outputs w.r.t. X* (linear MF kernel only): k_post_grad, after launch_post
+// with A (B) kept.  One task = one row tile j x `chunk` i-tiles of U_j = sum_i (L^{-1})_ij^T R_i
+// (+ C_ij^T R_B,i); the same task count as the forward by symmetry (row tile j has T - j steps).
+template <int NB> void launch_post_grad(const PostArgs& a, int batch, hipStream_t s);
 // tril(q_sqrt) zero padded / C = Lq^T Linv of the SVGP K_uu pipeline, into caller buffers (mfgp_svgp.hip)
 int svgp_posterior_factor(hipStream_t s, int nb, int m, int l, int d, const double* Z, int ldz, const double* thetas,
                           const double* q_sqrt, double jitter, void* ws, size_t ws_bytes, double* Li, double* C,

@@ -10,6 +10,8 @@
 //               colsum(B_i^2), A_i^T q_mu).  The last workgroup to arrive at a column tile's counter
 //               sums the group partials in group order, folds in K_diag(X*) and writes the outputs
 //               (SVGP: latent moments, mixing).
+//   k_post_grad the VJP of those outputs w.r.t. X* (linear MF kernel), behind the two launches above
+//               with A (B) kept: see "input gradients" below.
 //
 // Every sum has a fixed order and there are no floating-point atomics: two calls with the same
 // inputs give the same bits.  Cross-workgroup data inside k_post_out goes through sc1 stores /
@@ -103,15 +105,16 @@ __device__ __forceinline__ double post_kdiag(double f, const double* theta, int 
 }
 
 // sum over k < n of base[k * stride] in k order; the sc1 loads are issued eight at a time (one at a
-// time, a thread's sum cost a memory round trip per term)
+// time, a thread's sum cost a memory round trip per term; W = 32 for k_post_grad's long task lists)
+template <int W = 8>
 __device__ __forceinline__ double post_sum_coherent(const double* base, long stride, int n) {
     double s = 0.0;
-    for (int k0 = 0; k0 < n; k0 += 8) {
-        double v[8];
+    for (int k0 = 0; k0 < n; k0 += W) {
+        double v[W];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = k0 + j < n ? ld_coherent(base + (long)(k0 + j) * stride) : 0.0;
+        for (int j = 0; j < W; ++j) v[j] = k0 + j < n ? ld_coherent(base + (long)(k0 + j) * stride) : 0.0;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) s += v[j];
+        for (int j = 0; j < W; ++j) s += v[j];
     }
     return s;
 }
@@ -150,8 +153,12 @@ __global__ __launch_bounds__(NTHREADS) void k_post_a(PostArgs a) {
     double* ths = il + 2 * PMAXD;   // theta
     const int t = threadIdx.x, l = blockIdx.z;
     const int task = blockIdx.x / a.Ts, cs = blockIdx.x % a.Ts;
-    if (blockIdx.x == 0 && l == 0)
-        for (int e = t; e < a.Ts; e += NTHREADS) a.cnt[e] = 0;   // k_post_out's arrival counters
+    if (blockIdx.x == 0 && l == 0) {
+        // k_post_out's arrival counters; k_post_grad's: Ts column-tile counters, then Ts per batch entry
+        for (int e = t; e < a.Ts; e += NTHREADS) a.cnt[e] = 0;
+        if (a.gcnt)
+            for (int e = t; e < a.Ts * (1 + (int)gridDim.z); e += NTHREADS) a.gcnt[e] = 0;
+    }
     // task -> (row tile i, chunk ch)
     int i = 0, ch = task;
     for (; i < a.T; ++i) {
@@ -271,7 +278,8 @@ __global__ __launch_bounds__(NTHREADS) void k_post_out(PostArgs a) {
             const double sb = a.C ? post_sum(a.Bpart + o, st, nch) : 0.0;
             Ai[r * S + c] = sa;
             if (a.C) Bs[r * S + c] = sb;
-            if (a.Am) a.Am[((long)i * NB + r) * a.ldam + cs * NB + c] = sa;
+            if (a.Am) a.Am[l * a.sAm + ((long)i * NB + r) * a.ldam + cs * NB + c] = sa;
+            if (a.Bm) a.Bm[l * a.sAm + ((long)i * NB + r) * a.ldam + cs * NB + c] = sb;
         }
         __syncthreads();
         if (t < NB) {
@@ -387,5 +395,350 @@ void launch_post(const PostArgs& a, int batch, hipStream_t s) {
 
 template void launch_post<32>(const PostArgs&, int, hipStream_t);
 template void launch_post<64>(const PostArgs&, int, hipStream_t);
+
+// ---------------------------------------------------------------- input gradients (VJP w.r.t. X*)
+// With upstream gm (d / d mean) and gv (d / d var), and A (B) kept by the forward:
+//   GPR   R = Z gm^T - 2 A diag(gv),                         U = L^{-T} R
+//   SVGP  R_A = q_mu ggm^T - 2 A diag(ggv), R_B = 2 B diag(ggv),   U = Lm^{-T} R_A + C^T R_B   (per latent)
+//   gX[s, d] = sum_i U[i, s] dK(x_i, x*_s) / dx*_{s, d}
+//   dK / dx*_{s, d} = cL kL (x_{i, d} - x*_{s, d}) / lL_d^2 + cD kD (x_{i, d} - x*_{s, d}) / lD_d^2
+// One task = (row tile j, `chunk` consecutive i-tiles, column tile): the R tiles are formed on the
+// fly, the partial U_j is accumulated on the matrix core, the K(X_j, X*) tile is generated in LDS as
+// post_mf_tile does (its two terms kept apart) and U_j o K_j is contracted with the scaled
+// differences into D partial sums per column.  U and dK never exist in HBM.  The contraction is
+// linear in U, so a row tile's chunks contract independently.  Reduction in two stages, each by the
+// last workgroup to arrive at a counter: a batch entry's tasks of a column tile in task order (GPR:
+// that is gX), then the latents' sums in latent order.  (One stage over latents x tasks left a
+// single workgroup with 640 dependent-latency terms per output at Goku's single-bin SVGP.)
+
+// post_mf_tile with the entry split into its lL and lD terms, each multiplied by U:
+// KLs = U o cL kL, KDs = U o cD kD (cL = 1 | rho | rho^2, cD = 1 for HF x HF, else 0; masks as post_mf_tile)
+template <int NB>
+__device__ __forceinline__ void post_mf_tile_grad(double* KLs, double* KDs, const double* Us, const double* x1,
+                                                  const double* f1, const double* xs, const double* fs, int D,
+                                                  const double* il, const double* th) {
+    constexpr int S = TileCfg<NB>::S;
+    constexpr int RSTEP = NTHREADS / NB;
+    constexpr int NE = NB * NB / NTHREADS;
+    const int t = threadIdx.x, c = t % NB, rb = t / NB;
+    const double* xb = xs + c * PXS;
+    const double fb = fs[c];
+    const bool Lb = (fb == 0.0), Hb = (fb == 1.0);
+    const double vL = th[0], vD = th[1 + D], rho = th[2 + 2 * D];
+    for (int g = 0; g < NE; g += 4) {
+        const int r0 = rb + g * RSTEP;
+        const double* xa = x1 + r0 * PXS;
+        double kl[4] = {0.0, 0.0, 0.0, 0.0}, kd[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int d = 0; d < D; ++d) {
+            const double b = xb[d], lL = il[d], lD = il[PMAXD + d];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double df = xa[j * RSTEP * PXS + d] - b;
+                const double qL = df * lL, qD = df * lD;
+                kl[j] += qL * qL;
+                kd[j] += qD * qD;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { kl[j] *= -0.5; kd[j] *= -0.5; }
+        exp4(kl);
+        exp4(kd);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double fa = f1[r0 + j * RSTEP];
+            const bool La = (fa == 0.0), Ha = (fa == 1.0);
+            const double kL = vL * kl[j];
+            double wl = (La && Lb) ? kL : (!(Ha && Hb) ? kL * rho : kL * (rho * rho));
+            double wd = (Ha && Hb) ? vD * kd[j] : 0.0;
+            if (!(La || Ha) || !(Lb || Hb)) wl = wd = 0.0;
+            const int o = (r0 + j * RSTEP) * S + c;
+            const double u = Us[o];
+            KLs[o] = u * wl;
+            KDs[o] = u * wd;
+        }
+    }
+}
+
+// 4 tiles (L^{-1} | C or Z | R | R_B or gm), the staged inputs of the epilogue, flags, upstream
+// vectors, 1 / l, theta.  NB = 64: the staged inputs take the fourth tile's place (free by then);
+// four tiles and the inputs side by side would pass the 160 KB of a CU.
+template <int NB>
+constexpr size_t post_grad_smem() {
+    return sizeof(double) * (4 * (size_t)TileCfg<NB>::ELEMS + (NB == 64 ? 0 : 2 * NB * PXS) + 4 * NB + 2 * PMAXD + PTHETA);
+}
+static_assert(2 * 64 * PXS <= TileCfg<64>::ELEMS, "k_post_grad<64> stages its inputs in the fourth tile");
+
+template <int NB>
+__global__ __launch_bounds__(NTHREADS) void k_post_grad(PostArgs a) {
+    constexpr int S = TileCfg<NB>::S;
+    constexpr int E = TileCfg<NB>::ELEMS;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    double* Ls = smem;              // (L^{-1})_ij; epilogue: U o cL kL
+    double* Cs = Ls + E;            // SVGP C_ij, GPR Z_i tile; epilogue: U o cD kD
+    double* Rs = Cs + E;            // R_i (R_A,i); epilogue: U_j
+    double* Gs = Rs + E;            // SVGP R_B,i, GPR gm tile
+    double* x1 = NB == 64 ? Gs : Gs + E;   // NB x PXS: cached rows of tile j (epilogue)
+    double* xs = x1 + NB * PXS;            // NB x PXS: X* rows of the column tile (epilogue)
+    double* f1 = smem + 4 * E + (NB == 64 ? 0 : 2 * NB * PXS);
+    double* fs = f1 + NB;
+    double* gms = fs + NB;          // SVGP: ggm_l of the column tile
+    double* gvs = gms + NB;         // gv (SVGP: ggv_l) of the column tile
+    double* il = gvs + NB;          // [1 / lL | 1 / lD]
+    double* ths = il + 2 * PMAXD;
+    __shared__ int last;
+    const int t = threadIdx.x, l = blockIdx.z, L = (int)gridDim.z;
+    const int task = blockIdx.x / a.Ts, cs = blockIdx.x % a.Ts;
+    // task -> (row tile j, chunk ch): row tile j has T - j steps (all T with C), the forward's counts mirrored
+    int jj = 0, ch = task;
+    for (; jj < a.T; ++jj) {
+        const int nch = ((a.full ? a.T : jj + 1) + a.chunk - 1) / a.chunk;
+        if (ch < nch) break;
+        ch -= nch;
+    }
+    if (jj >= a.T) return;   // (never: the grid is post_ntasks x Ts)
+    const int j = a.full ? jj : a.T - 1 - jj;
+    const int m0 = ch * a.chunk;
+    const int mend = a.full ? a.T : jj + 1;
+    const int m1 = m0 + a.chunk < mend ? m0 + a.chunk : mend;
+    const int D = a.D;
+    const double* tp = a.theta + l * a.stheta;
+    for (int e = t; e < theta_size(D); e += NTHREADS) ths[e] = tp[e];
+    if (t < D) {
+        il[t] = rcp_nr(tp[1 + t]);
+        il[PMAXD + t] = rcp_nr(tp[2 + D + t]);
+    }
+    if (t < NB) {   // the column tile's upstream vectors (rows beyond nstar: zero)
+        const int s = cs * NB + t;
+        double vm = 0.0, vv = 0.0;
+        if (s < a.nstar) {
+            if (a.Zc) {
+                if (a.gvar) vv = a.gvar[s];
+            } else if (a.W) {   // ggm = gm W, ggv = gv (W o W), summed in output order
+                for (int c = 0; c < a.p; ++c) {
+                    const double w = a.W[(long)c * L + l];
+                    if (a.gmean) vm += a.gmean[(long)s * a.ldgm + c] * w;
+                    if (a.gvar) vv += a.gvar[(long)s * a.p + c] * (w * w);
+                }
+            } else {
+                if (a.gmean) vm = a.gmean[(long)s * a.ldgm + l];
+                if (a.gvar) vv = a.gvar[(long)s * a.p + l];
+            }
+        }
+        gms[t] = vm;
+        gvs[t] = vv;
+    }
+    __syncthreads();
+    const double* Li = a.Li + l * a.sL;
+    const double* Cm = a.C ? a.C + l * a.sC : nullptr;
+    const double* Am = a.Am + l * a.sAm;
+    // One memory round trip a step, hidden behind the previous step's products (k_post_a's scheme):
+    // every tile and vector of the next product is fetched into registers before the current one runs.
+    constexpr int NP = NB * NB / 2 / NTHREADS;   // 16-byte pairs of a tile per thread
+    constexpr int NBLK = TileCfg<NB>::NBLK;
+    Acc<NB> accU;
+    acc_zero(accU);
+    if (a.Zc) {
+        // GPR: R_i = Z_i gm^T - 2 A_i diag(gv) in the accumulator layout, then U_j += (L^{-1})_ij^T R_i
+        const bool hasM = a.gmean != nullptr, hasV = a.gvar != nullptr;
+        TileRegs<NB> rl, rz;
+        double rg[2 * NP], ra[NBLK][4];
+        auto fetch_zg = [&](int i, int cy, bool g) {   // Z tile (i, cy) and, with g, the gm tile cy
+            tile_fetch<NB>(rz, a.Zc + (long)i * NB * a.ldz + (long)cy * NB, a.ldz);
+            if (g) {
+#pragma unroll
+                for (int q = 0; q < 2 * NP; ++q) {
+                    const int e = t + q * NTHREADS, r = e / NB, c = e % NB, s = cs * NB + r, cc = cy * NB + c;
+                    rg[q] = (s < a.nstar && cc < a.p) ? a.gmean[(long)s * a.ldgm + cc] : 0.0;
+                }
+            }
+        };
+        auto fetch_la = [&](int i) {   // (L^{-1})_ij and A_i's entries of this thread's accumulator slots
+            tile_fetch<NB>(rl, Li + (long)i * NB * a.ldl + (long)j * NB, a.ldl);
+            if (hasV) {
+#pragma unroll
+                for (int q = 0; q < NBLK; ++q)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        ra[q][r] = Am[((long)i * NB + acc_row<NB>(q, r)) * a.ldam + cs * NB + acc_col<NB>(q)];
+            }
+        };
+        if (m0 < m1) {
+            const int i = a.full ? m0 : j + m0;
+            if (hasM) fetch_zg(i, 0, true);
+            fetch_la(i);
+        }
+        for (int m = m0; m < m1; ++m) {
+            const int i = a.full ? m : j + m;
+            Acc<NB> accR;
+            acc_zero(accR);
+            if (hasM)
+                for (int cy = 0; cy < a.Tp; ++cy) {
+                    __syncthreads();   // the previous products' readers of Cs / Gs (and of Ls / Rs)
+                    tile_put<NB>(Cs, rz);
+                    if (a.Tp > 1 || m == m0) {   // one gm tile: staged once
+#pragma unroll
+                        for (int q = 0; q < 2 * NP; ++q) {
+                            const int e = t + q * NTHREADS;
+                            Gs[(e / NB) * S + e % NB] = rg[q];
+                        }
+                    }
+                    if (cy + 1 < a.Tp) fetch_zg(i, cy + 1, true);
+                    else if (m + 1 < m1) fetch_zg(i + 1, 0, a.Tp > 1);
+                    __syncthreads();
+                    tile_mma<NB, false, true>(accR, Cs, Gs, 1.0);
+                }
+            if (hasV) {
+#pragma unroll
+                for (int q = 0; q < NBLK; ++q)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) accR.v[q][r] -= 2.0 * ra[q][r] * gvs[acc_col<NB>(q)];
+            }
+            if (!hasM) __syncthreads();   // the previous step's readers of Ls / Rs
+            tile_put<NB>(Ls, rl);
+            acc_to_lds<NB>(accR, Rs);
+            if (m + 1 < m1) fetch_la(i + 1);
+            __syncthreads();
+            tile_mma<NB, true, false>(accU, Ls, Rs, 1.0);
+        }
+    } else {
+        // SVGP: R_A,i = q_mu_i ggm^T - 2 A_i diag(ggv) (i >= j: Lm^{-1} is lower), R_B,i = 2 B_i diag(ggv);
+        // U_j += (Lm^{-1})_ij^T R_A,i + C_ij^T R_B,i
+        const bool hasB = a.gvar != nullptr;
+        const double* Bm = hasB ? a.Bm + l * a.sAm : nullptr;
+        const double* qm = a.qmu + (long)l * a.T * NB;
+        TileRegs<NB> rl, rc, ra, rb;
+        double rq[NP];
+        auto fetch = [&](int i) {
+            if (i >= j) {
+                tile_fetch<NB>(rl, Li + (long)i * NB * a.ldl + (long)j * NB, a.ldl);
+                tile_fetch<NB>(ra, Am + (long)i * NB * a.ldam + cs * NB, a.ldam);
+#pragma unroll
+                for (int q = 0; q < NP; ++q) rq[q] = qm[i * NB + (t + q * NTHREADS) / (NB / 2)];
+            }
+            if (hasB) {
+                tile_fetch<NB>(rc, Cm + (long)i * NB * a.ldc + (long)j * NB, a.ldc);
+                tile_fetch<NB>(rb, Bm + (long)i * NB * a.ldam + cs * NB, a.ldam);
+            }
+        };
+        if (m0 < m1) fetch(a.full ? m0 : j + m0);
+        for (int m = m0; m < m1; ++m) {
+            const int i = a.full ? m : j + m;
+            const bool lower = i >= j;
+            __syncthreads();   // the previous step's readers
+            if (lower) tile_put<NB>(Ls, rl);
+            if (hasB) tile_put<NB>(Cs, rc);
+#pragma unroll
+            for (int q = 0; q < NP; ++q) {
+                const int pr = t + q * NTHREADS, row = pr / (NB / 2), c = 2 * (pr % (NB / 2));
+                const double g0 = gvs[c], g1 = gvs[c + 1];
+                if (lower) {
+                    f64x2 v;
+                    v[0] = rq[q] * gms[c] - 2.0 * ra.v[q][0] * g0;
+                    v[1] = rq[q] * gms[c + 1] - 2.0 * ra.v[q][1] * g1;
+                    *reinterpret_cast<f64x2*>(Rs + row * S + c) = v;
+                }
+                if (hasB) {
+                    f64x2 v;
+                    v[0] = 2.0 * rb.v[q][0] * g0;
+                    v[1] = 2.0 * rb.v[q][1] * g1;
+                    *reinterpret_cast<f64x2*>(Gs + row * S + c) = v;
+                }
+            }
+            if (m + 1 < m1) fetch(i + 1);
+            __syncthreads();
+            if (lower) tile_mma<NB, true, false>(accU, Ls, Rs, 1.0);
+            if (hasB) tile_mma<NB, true, false>(accU, Cs, Gs, 1.0);
+        }
+    }
+    // ---- epilogue: U_j o K(X_j, X*) contracted with (x_i - x*_s) / l^2
+    __syncthreads();   // the last product's readers
+    acc_to_lds<NB>(accU, Rs);
+    for (int e = t; e < NB * D; e += NTHREADS) {
+        const int r = e / D, d = e % D, gr = j * NB + r, gs = cs * NB + r;
+        x1[r * PXS + d] = gr < a.n1 ? a.X1[(long)gr * a.ldx1 + d] : 0.0;
+        xs[r * PXS + d] = gs < a.nstar ? a.Xs[(long)gs * a.ldxs + d] : 0.0;
+    }
+    if (t < NB) {
+        const int gr = j * NB + t, gs = cs * NB + t;
+        f1[t] = gr < a.n1 ? a.X1[(long)gr * a.ldx1 + D] : -1.0;
+        fs[t] = gs < a.nstar ? a.Xs[(long)gs * a.ldxs + D] : -1.0;
+    }
+    __syncthreads();
+    post_mf_tile_grad<NB>(Ls, Cs, Rs, x1, f1, xs, fs, D, il, ths);
+    __syncthreads();
+    // thread (column sl, dimension group dg): dimensions dg, dg + NG, ..; rows in row order
+    constexpr int NG = NTHREADS / NB, ND = PMAXD / NG;
+    const int sl = t % NB, dg = t / NB;
+    double acc[ND], wl[ND], wd[ND], xv[ND];
+#pragma unroll
+    for (int k = 0; k < ND; ++k) {
+        const int d = dg + k * NG;
+        const bool in = d < D;
+        acc[k] = 0.0;
+        wl[k] = in ? il[d] * il[d] : 0.0;
+        wd[k] = in ? il[PMAXD + d] * il[PMAXD + d] : 0.0;
+        xv[k] = in ? xs[sl * PXS + d] : 0.0;
+    }
+    for (int r = 0; r < NB; ++r) {
+        const double pl = Ls[r * S + sl], pd = Cs[r * S + sl];
+#pragma unroll
+        for (int k = 0; k < ND; ++k) {
+            const int d = dg + k * NG;
+            if (d < D) acc[k] += (pl * wl[k] + pd * wd[k]) * (x1[r * PXS + d] - xv[k]);
+        }
+    }
+    const long pstride = (long)a.Ts * D * NB;
+    double* gp = a.gpart + ((long)l * a.ntask + task) * pstride + (long)cs * D * NB;
+#pragma unroll
+    for (int k = 0; k < ND; ++k) {
+        const int d = dg + k * NG;
+        if (d < D) st_coherent(gp + d * NB + sl, acc[k]);
+    }
+    drain_stores();
+    __syncthreads();
+    if (t == 0) last = arrive(a.gcnt + (1 + l) * a.Ts + cs) == a.ntask - 1;
+    __syncthreads();
+    if (!last) return;
+    // ---- the batch entry's gradient of this column tile, by its last workgroup: partials in task order
+    const double* gl = a.gpart + (long)l * a.ntask * pstride + (long)cs * D * NB;
+    for (int e = t; e < NB * D; e += NTHREADS) {
+        const double v = post_sum_coherent<32>(gl + e, pstride, a.ntask);
+        if (L == 1) {
+            const int s = cs * NB + e % NB;
+            if (s < a.nstar) a.gX[(long)s * a.ldgx + e / NB] = v;
+        } else {
+            st_coherent(a.glat + ((long)l * a.Ts + cs) * D * NB + e, v);
+        }
+    }
+    if (L > 1) {
+        drain_stores();
+        __syncthreads();
+        if (t == 0) last = arrive(a.gcnt + cs) == L - 1;
+        __syncthreads();
+        if (!last) return;
+        // ---- gX, by the column tile's last batch entry: the latents' gradients in latent order
+        for (int e = t; e < NB * D; e += NTHREADS) {
+            const int s = cs * NB + e % NB;
+            if (s >= a.nstar) continue;
+            a.gX[(long)s * a.ldgx + e / NB] =
+                post_sum_coherent<32>(a.glat + (long)cs * D * NB + e, (long)a.Ts * D * NB, L);
+        }
+    }
+    if (t < NB && cs * NB + t < a.nstar) a.gX[(long)(cs * NB + t) * a.ldgx + D] = 0.0;   // the fidelity column
+}
+
+template <int NB>
+void launch_post_grad(const PostArgs& a, int batch, hipStream_t s) {
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_post_grad<NB>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)post_grad_smem<NB>());
+        attr = true;
+    }
+    hipLaunchKernelGGL(k_post_grad<NB>, dim3(a.ntask * a.Ts, 1, batch), dim3(NTHREADS), post_grad_smem<NB>(), s, a);
+}
+
+template void launch_post_grad<32>(const PostArgs&, int, hipStream_t);
+template void launch_post_grad<64>(const PostArgs&, int, hipStream_t);
 
 }  // namespace mfgp

@@ -9,6 +9,12 @@ launches, no Gram of X, no factorization, no parameter upload and no host read o
 The cache is a *snapshot*: assigning to the model or training it does not change what the cached
 ``predict_f`` returns until ``update_cache()`` is called.  ``fused_predict_f`` never uses the cache:
 it is the model's own ``predict_f`` at the model's current parameters.
+
+Input gradients: ``predict_f_vjp(Xnew, grad_mean, grad_var)`` returns the marginal prediction and the
+vector-Jacobian product with respect to ``Xnew`` from one call (``mfgp_*_posterior_predict_vjp``: the
+predict call's two launches and one more), and the cached marginal ``predict_f`` of a torch ``Xnew``
+with ``requires_grad=True`` is attached to autograd through it.  The fidelity column of ``Xnew``
+enters the kernels only through exact ``== 0`` / ``== 1`` tests, so its gradient is exactly zero.
 """
 from __future__ import annotations
 
@@ -41,8 +47,42 @@ def _cache_type(value) -> PrecomputeCacheType:
     return PrecomputeCacheType(str(value).lower())
 
 
+def _wants_grad(Xnew) -> bool:
+    return isinstance(Xnew, torch.Tensor) and Xnew.requires_grad and torch.is_grad_enabled()
+
+
+def _upstream(g, shape, device, what):
+    """An upstream gradient as a dense device tensor of `shape` (None stays None: zero)."""
+    if g is None:
+        return None
+    g = to_dev(g, device)
+    if tuple(g.shape) != tuple(shape):
+        raise ValueError(f"predict_f_vjp: {what} has shape {tuple(g.shape)}, expected {tuple(shape)}")
+    return g
+
+
+class _PredictFn(torch.autograd.Function):
+    """The cached marginal predict_f as an autograd node: backward is the VJP call on the cache block
+    the forward ran on (a TENSOR cache replaced by update_cache() in between stays alive here)."""
+
+    @staticmethod
+    def forward(ctx, Xnew, post):
+        ctx.post, ctx.cache = post, post.cache
+        ctx.save_for_backward(Xnew)
+        mean, var = post._marginal(Xnew)
+        return mean, var
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_mean, grad_var):
+        (Xnew,) = ctx.saved_tensors
+        _, _, gX = ctx.post._vjp(ctx.cache, Xnew, grad_mean, grad_var)
+        return gX.to(device=Xnew.device, dtype=Xnew.dtype), None
+
+
 class _Posterior:
-    """Shared surface: predict_f / fused_predict_f / update_cache and the cache buffer policy."""
+    """Shared surface: predict_f / predict_f_vjp / fused_predict_f / update_cache and the cache buffer
+    policy."""
 
     def __init__(self, model, precompute_cache):
         self.model = model
@@ -84,6 +124,32 @@ class _Posterior:
             raise info_error(bad, what)
         self.cache, self._valid = buf, True
 
+    def predict_f_vjp(self, Xnew, grad_mean, grad_var=None):
+        """The marginal predict_f at the snapshot and its vector-Jacobian product w.r.t. Xnew:
+        ``(mean, var, grad_X)`` with ``grad_X[s, k] = sum_c grad_mean[s, c] dmean[s, c] / dXnew[s, k]
+        + sum_c grad_var[s, c] dvar[s, c] / dXnew[s, k]``, shape [N*, D + 1], fidelity column exactly 0.
+        ``grad_mean`` / ``grad_var`` are [N*, P] (None: zero; GPR also takes ``grad_var`` [N*], the
+        gradient w.r.t. the one variance column that predict_f tiles over P).  mean / var carry
+        predict_f's bits.  Like predict_f it is the snapshot's until update_cache()."""
+        if self._precompute_cache is PrecomputeCacheType.NOCACHE:
+            raise NotImplementedError("predict_f_vjp: a NOCACHE posterior has no cached factors to differentiate "
+                                      "through; use a TENSOR or VARIABLE cache")
+        self._check_vjp()
+        mean, var, gX = self._vjp(self.cache, Xnew, grad_mean, grad_var)
+        return as_result(mean), as_result(var), as_result(gX)
+
+    def _check_vjp(self):
+        pass
+
+    def _attached(self, Xnew):
+        """predict_f of a requires_grad Xnew: outputs attached to autograd (backward = the VJP call)."""
+        if self._precompute_cache is PrecomputeCacheType.NOCACHE:
+            raise NotImplementedError("predict_f of an Xnew that requires grad needs a cached posterior "
+                                      "(TENSOR or VARIABLE)")
+        self._check_vjp()
+        mean, var = _PredictFn.apply(Xnew, self)
+        return as_result(mean), as_result(var)
+
     def _require_cache(self, eng: Engine):
         if not self._valid:
             raise MFGPError("posterior: the cache is not valid (its last update failed); call update_cache()")
@@ -124,6 +190,11 @@ class GPRPosterior(_Posterior):
         full_cov, [P, N*, N*]).  Uploads Xnew when it is not a device tensor, enqueues, returns."""
         if full_output_cov:
             raise NotImplementedError("predict_f(full_output_cov=True): GPR has no output covariance to return")
+        if _wants_grad(Xnew):
+            if full_cov:
+                raise NotImplementedError("predict_f(full_cov=True) of an Xnew that requires grad: only the "
+                                          "marginal form has an input gradient")
+            return self._attached(Xnew)
         if self._precompute_cache is PrecomputeCacheType.NOCACHE:
             return self.fused_predict_f(Xnew, full_cov=full_cov)
         eng = Engine.get(self.cache.device if self.cache is not None else None)
@@ -144,6 +215,40 @@ class GPRPosterior(_Posterior):
         if full_cov:
             return as_result(mean), as_result(cov[None].expand(p, -1, -1).contiguous())
         return as_result(mean), as_result(var[:, None].expand(-1, p).contiguous())
+
+    def _marginal(self, Xnew):
+        mean, var = self.predict_f(Xnew.detach())
+        return mean.as_subclass(torch.Tensor), var.as_subclass(torch.Tensor)
+
+    def _check_vjp(self):
+        if self._nlf:
+            raise NotImplementedError("predict_f_vjp: the graph kernel's input gradient (a derivative per source) "
+                                      "is not built; only the linear multi-fidelity kernel has one")
+
+    def _vjp(self, cache, Xnew, grad_mean, grad_var):
+        eng = Engine.get(cache.device if cache is not None else None)
+        self._require_cache(eng)
+        n, p, d = self._shape
+        Xs = to_dev(Xnew, eng.device)
+        ns = Xs.shape[0]
+        gm = _upstream(grad_mean, (ns, p), eng.device, "grad_mean")
+        gv = None
+        if grad_var is not None:
+            gv = to_dev(grad_var, eng.device)
+            if gv.dim() == 2:   # the variance is one column tiled over P: its upstream gradients add up
+                gv = _upstream(gv, (ns, p), eng.device, "grad_var").sum(dim=1)
+            gv = _upstream(gv, (ns,), eng.device, "grad_var")
+        f64 = dict(dtype=torch.float64, device=eng.device)
+        mean, var = torch.empty((ns, p), **f64), torch.empty((ns,), **f64)
+        gX = torch.empty((ns, d + 1), **f64)   # every entry is written by the call (fidelity column: 0)
+        if ns:
+            lib = eng.lib
+            ws = eng.workspace("post_vjp", eng._size(lib.mfgp_gpr_posterior_predict_vjp_workspace_size, self._nlf, n,
+                                                     p, d, ns))
+            check(lib.mfgp_gpr_posterior_predict_vjp(eng.h, self._nlf, n, p, d, ns, ptr(cache), cache.numel(), ptr(Xs),
+                                                     Xs.shape[1], ptr(ws), ws.numel(), ptr(mean), p, ptr(var), ptr(gm),
+                                                     p, ptr(gv), ptr(gX), d + 1), "mfgp_gpr_posterior_predict_vjp")
+        return mean, var[:, None].expand(-1, p).contiguous(), gX
 
 
 class SVGPPosterior(_Posterior):
@@ -180,6 +285,11 @@ class SVGPPosterior(_Posterior):
     def predict_f(self, Xnew, full_cov: bool = False, full_output_cov: bool = False):
         """The model's predict_f at the snapshot: mean [N*, P]; var [N*, P], or the model's
         covariance forms (not cached, see the class docstring)."""
+        if _wants_grad(Xnew):
+            if full_cov or full_output_cov:
+                raise NotImplementedError("predict_f(full_cov / full_output_cov) of an Xnew that requires grad: "
+                                          "only the marginal form has an input gradient")
+            return self._attached(Xnew)
         if self._precompute_cache is PrecomputeCacheType.NOCACHE:
             return self.fused_predict_f(Xnew, full_cov=full_cov, full_output_cov=full_output_cov)
         eng = Engine.get(self.cache.device if self.cache is not None else None)
@@ -203,3 +313,28 @@ class SVGPPosterior(_Posterior):
                                                   self.cache.numel(), ptr(Xs), Xs.shape[1], ptr(ws), ws.numel(),
                                                   ptr(f_mu), ptr(f_var)), "mfgp_svgp_posterior_predict")
         return as_result(f_mu), as_result(f_var)
+
+    def _marginal(self, Xnew):
+        f_mu, f_var = self.predict_f(Xnew.detach())
+        return f_mu.as_subclass(torch.Tensor), f_var.as_subclass(torch.Tensor)
+
+    def _vjp(self, cache, Xnew, grad_mean, grad_var):
+        eng = Engine.get(cache.device if cache is not None else None)
+        self._require_cache(eng)
+        m, L, p, d, mixed = self._shape
+        Xs = to_dev(Xnew, eng.device)
+        ns = Xs.shape[0]
+        gm = _upstream(grad_mean, (ns, p), eng.device, "grad_mean")
+        gv = _upstream(grad_var, (ns, p), eng.device, "grad_var")
+        f64 = dict(dtype=torch.float64, device=eng.device)
+        f_mu, f_var = torch.empty((ns, p), **f64), torch.empty((ns, p), **f64)
+        gX = torch.empty((ns, d + 1), **f64)   # every entry is written by the call (fidelity column: 0)
+        if ns:
+            lib = eng.lib
+            ws = eng.workspace("post_vjp", eng._size(lib.mfgp_svgp_posterior_predict_vjp_workspace_size, ns, m, L, p,
+                                                     d))
+            check(lib.mfgp_svgp_posterior_predict_vjp(eng.h, ns, m, L, p, d, 1 if mixed else 0, ptr(cache),
+                                                      cache.numel(), ptr(Xs), Xs.shape[1], ptr(ws), ws.numel(),
+                                                      ptr(f_mu), ptr(f_var), ptr(gm), p, ptr(gv), ptr(gX), d + 1),
+                  "mfgp_svgp_posterior_predict_vjp")
+        return f_mu, f_var, gX
