@@ -426,6 +426,34 @@ int mfgp_svgp_posterior_predict_vjp(mfgp_handle_t h, int nstar, int m, int l, in
                                     size_t ws_bytes, double* f_mu, double* f_var, const double* gmean, int ldgm,
                                     const double* gvar, double* gX, int ldgx);
 
+/* Leave-group-out cross-validation from a GPR cache, at the cache's hyper-parameters: for each group
+ * S of training rows, what a model built without those rows predicts for them, in closed form from
+ * the cached L^{-1} and Z alone (C = L^{-1}[:, S], G = C^T C, H = C^T Z): no Gram, no factorization
+ * of K, no kernel evaluation, for nlf = 0 and nlf > 0 alike.
+ *   offsets [ngroups + 1], rows [nrows]: device ints; group g is rows[offsets[g] .. offsets[g + 1]),
+ *            1 .. gmax (<= 32) distinct training-row indices, offsets[0] = 0, offsets[ngroups] = nrows.
+ *            A row may appear in several groups.
+ *   resid    [nrows x p] (ldr): E = y_S - mean_{S|-S} = G^{-1} H; the held-out mean is Y[rows] - resid.
+ *   cov      [nrows x gmax] (ldc; may be NULL): row r holds its row of its group's latent covariance
+ *            Sigma_f = G^{-1} - s2 I (s2: the cached likelihood variance; what predict_f(full_cov) of
+ *            the model without S returns), zero beyond the group's size.
+ *   logdens  [ngroups x p]: the joint log predictive density of the group's observations per output,
+ *            -1/2 H_c^T G^{-1} H_c + 1/2 log det G - |S| / 2 log 2 pi.
+ *   info     [ngroups]: 0, or the first non-positive pivot of the group's G (1-based within the
+ *            group); -1 on every group when the table is malformed (a size outside 1..gmax, a row
+ *            outside 0..n-1): nothing else is written then.
+ * Two launches; fixed-order sums and no floating-point atomics (the same inputs give the same bits);
+ * nothing is allocated, the cache is only read, the host reads no device word.  gmax > 32 or a
+ * non-positive count: MFGP_ERR_ARG; a cache or workspace smaller than the *_size calls report:
+ * MFGP_ERR_WORKSPACE before any device work; ngroups = 0 is a no-op.  Use the cache at the tile size
+ * it was built for. */
+int mfgp_gpr_posterior_leave_out_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int ngroups, int nrows,
+                                                size_t* bytes);
+int mfgp_gpr_posterior_leave_out(mfgp_handle_t h, int nlf, int n, int p, int d, const void* cache, size_t cache_bytes,
+                                 int ngroups, const int* offsets, const int* rows, int nrows, int gmax, void* ws,
+                                 size_t ws_bytes, double* resid, int ldr, double* cov, int ldc, double* logdens,
+                                 int* info);
+
 /* Diagnostic: one v_mfma_f64_16x16x4_f64 with A[i][k] = 4i+k+1, B[k][j] = 100k+j;
  * writes C (16x16 row-major, device). */
 int mfgp_selftest_mfma(mfgp_handle_t h, double* out);

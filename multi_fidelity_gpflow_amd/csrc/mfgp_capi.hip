@@ -982,6 +982,32 @@ static int gpr_posterior_predict_impl(mfgp_handle_t h, int nlf, int n, int p, in
     return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
 }
 
+// Leave-group-out workspace: the task table, the arrival counters and the chunk partials.
+// Tasks: first fit in order closes a task only when the next group does not fit, so every task but
+// the last holds at least 33 - gmax columns, and two consecutive tasks together more than 32.
+// Chunks: 4 steps of 32 rows (a task at Goku's 37 steps is spread over 10 workgroups), longer
+// beyond 128 steps so that the last workgroup sums at most 32 partials.
+struct LoLayout {
+    int chunk, nch, ny, ntmax;
+    int *tab, *cnt;
+    double* part;
+    size_t bytes;
+};
+static LoLayout lo_layout(int n, int p, int ngroups, int nrows, int gmax, void* ws) {
+    LoLayout L{};
+    const int T32 = ceil_div(n, 32);
+    L.chunk = T32 > 128 ? ceil_div(T32, 32) : 4;
+    L.nch = ceil_div(T32, L.chunk);
+    L.ny = ceil_div(p, 32 * LO_PT);
+    L.ntmax = std::min(ngroups, std::min((nrows - 1) / (LO_W + 1 - gmax) + 1, 2 * (nrows / (LO_W + 1)) + 1));
+    Carve c(ws);
+    L.tab = c.take<int>((size_t)L.ntmax + 2);
+    L.cnt = c.take<int>((size_t)L.ntmax * L.ny);
+    L.part = c.take<double>((size_t)L.ntmax * L.nch * L.ny * 32 * 32 * (1 + LO_PT));
+    L.bytes = c.off + 256;
+    return L;
+}
+
 // SVGP cache: [Z: m x (d + 1)][thetas: l x G][W: p x l][q_mu^T: l x Mpad, zero padded]
 //             [Lm^{-1}: l x Mpad x Mpad][C = Lq^T Lm^{-1}: l x Mpad x Mpad]
 struct SvgpCache {
@@ -1792,6 +1818,43 @@ int mfgp_gpr_posterior_predict_vjp(mfgp_handle_t h, int nlf, int n, int p, int d
                                               ldm, var, nullptr, 0, &g);
     return gpr_posterior_predict_impl<32>(h, nlf, n, p, d, nstar, cache, cache_bytes, Xs, ldxs, ws, ws_bytes, mean,
                                           ldm, var, nullptr, 0, &g);
+}
+
+int mfgp_gpr_posterior_leave_out_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int ngroups, int nrows,
+                                                size_t* bytes) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nlf < 0 || nlf > MFGP_MAX_LF || n < 1 || p < 1 || ngroups < 1 || nrows < ngroups || !bytes)
+        return MFGP_ERR_ARG;
+    *bytes = lo_layout(n, p, ngroups, nrows, LO_W, nullptr).bytes;   // groups of any size up to 32
+    return MFGP_OK;
+}
+
+int mfgp_gpr_posterior_leave_out(mfgp_handle_t h, int nlf, int n, int p, int d, const void* cache, size_t cache_bytes,
+                                 int ngroups, const int* offsets, const int* rows, int nrows, int gmax, void* ws,
+                                 size_t ws_bytes, double* resid, int ldr, double* cov, int ldc, double* logdens,
+                                 int* info) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nlf < 0 || nlf > MFGP_MAX_LF || ngroups < 0 || gmax < 1 || gmax > LO_W) return MFGP_ERR_ARG;
+    if (ngroups == 0) return MFGP_OK;
+    if (n < 1 || p < 1 || nrows < ngroups || !cache || !offsets || !rows || !ws || !resid || !logdens || !info ||
+        ldr < p || (cov && ldc < gmax))
+        return MFGP_ERR_ARG;
+    const GprCache c = gpr_cache_layout(h->nb, nlf, n, p, d, const_cast<void*>(cache));
+    const LoLayout L = lo_layout(n, p, ngroups, nrows, gmax, ws);
+    if (cache_bytes < c.bytes || ws_bytes < L.bytes) return MFGP_ERR_WORKSPACE;
+    LoArgs a{};
+    a.LZ = c.LZ; a.ldr = c.ldr; a.npad = c.npad;
+    a.noise = c.theta + c.G - 1;   // the likelihood variance closes both theta layouts
+    a.n = n; a.p = p;
+    a.ngroups = ngroups; a.nrows = nrows; a.gmax = gmax;
+    a.offsets = offsets; a.rows = rows;
+    a.ntmax = L.ntmax; a.chunk = L.chunk; a.nch = L.nch; a.ny = L.ny;
+    a.tab = L.tab; a.cnt = L.cnt; a.part = L.part;
+    a.resid = resid; a.ldres = ldr; a.cov = cov; a.ldc = ldc; a.logdens = logdens; a.info = info;
+    launch_leave_out(a, h->stream);
+    return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
 }
 
 int mfgp_svgp_posterior_size(mfgp_handle_t h, int m, int l, int p, int d, size_t* bytes) {

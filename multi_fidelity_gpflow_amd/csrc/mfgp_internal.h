@@ -216,6 +216,31 @@ template <int NB> void launch_post(const PostArgs& a, int batch, hipStream_t s);
 // with A (B) kept.  One task = one row tile j x `chunk` i-tiles of U_j = sum_i (L^{-1})_ij^T R_i
 // (+ C_ij^T R_B,i); the same task count as the forward by symmetry (row tile j has T - j steps).
 template <int NB> void launch_post_grad(const PostArgs& a, int batch, hipStream_t s);
+// Leave-group-out prediction from the GPR cache (mfgp_leave_out.hip): k_lo_pack packs whole
+// consecutive groups into tasks of at most LO_W columns, k_lo accumulates C^T [C | Z] of a task's
+// gathered columns C = L^{-1}[:, S] over chunks of 32-row steps and its last workgroup factors the
+// block-diagonal G = C^T C and writes the outputs.
+constexpr int LO_W = 32;    // columns of a task = the largest group
+constexpr int LO_PT = 3;    // 32-column blocks of Z one workgroup carries (96 outputs)
+struct LoArgs {
+    const double* LZ; long ldr; int npad;     // cached [L^{-1} | Z] rows (read-only)
+    const double* noise;                      // the cached likelihood variance
+    int n, p;
+    int ngroups, nrows, gmax;
+    const int* offsets; const int* rows;      // group g: rows[offsets[g] .. offsets[g + 1])
+    int ntmax;                                // task slots (lo_layout's bound on the packing)
+    int chunk, nch;                           // 32-row steps per chunk, chunks of n rows
+    int ny;                                   // blocks of 32 LO_PT outputs
+    int* tab;                                 // [ntmax + 2]: task count, then each task's first group, then ngroups
+    int* cnt;                                 // [ntmax][ny] arrival counters (zeroed by k_lo_pack)
+    double* part;                             // [ntmax][nch][ny][32][32 (1 + LO_PT)] chunk partials
+    double* resid; long ldres;                // [nrows x p]  E = y_S - mu
+    double* cov; long ldc;                    // [nrows x gmax] rows of the groups' Sigma_f (nullptr: skipped)
+    double* logdens;                          // [ngroups x p]
+    int* info;                                // [ngroups]
+};
+void launch_leave_out(const LoArgs& a, hipStream_t s);
+
 // tril(q_sqrt) zero padded / C = Lq^T Linv of the SVGP K_uu pipeline, into caller buffers (mfgp_svgp.hip)
 int svgp_posterior_factor(hipStream_t s, int nb, int m, int l, int d, const double* Z, int ldz, const double* thetas,
                           const double* q_sqrt, double jitter, void* ws, size_t ws_bytes, double* Li, double* C,

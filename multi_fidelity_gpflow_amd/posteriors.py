@@ -19,7 +19,9 @@ enters the kernels only through exact ``== 0`` / ``== 1`` tests, so its gradient
 from __future__ import annotations
 
 import enum
+from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from ._lib import MFGPError, check, info_error, ptr
@@ -59,6 +61,118 @@ def _upstream(g, shape, device, what):
     if tuple(g.shape) != tuple(shape):
         raise ValueError(f"predict_f_vjp: {what} has shape {tuple(g.shape)}, expected {tuple(shape)}")
     return g
+
+
+MAX_GROUP = 32   # rows of one left-out group (include/mfgp.h mfgp_gpr_posterior_leave_out: gmax <= 32)
+
+
+class LeaveOutResult(NamedTuple):
+    """What ``GPRPosterior.leave_out`` returns: R rows over G groups, group after group."""
+    rows: np.ndarray            # int64 [R] training-row indices, ascending within a group
+    group: np.ndarray           # int64 [R] the group each returned row belongs to
+    mean: torch.Tensor          # [R, P] held-out mean
+    var: torch.Tensor           # [R, P] marginal variance of f, tiled over P as predict_f tiles it
+    log_density: torch.Tensor   # [G, P] joint log predictive density of each group's observations
+    cov: Optional[torch.Tensor] = None   # [G, gmax, gmax] covariance of f_S, zero outside each group's block
+
+
+def _index_array(g, what):
+    a = np.asarray(g)
+    if a.size and (a.dtype == bool or not np.issubdtype(a.dtype, np.integer)):
+        raise ValueError(f"leave_out: {what} must hold integers, got dtype {a.dtype}")
+    return a.astype(np.int64)
+
+
+def _too_large(k, size):
+    return ValueError(f"leave_out: group {k} has {size} rows; at most {MAX_GROUP} rows can be left out together")
+
+
+def _groups_from_labels(labels, n):
+    """Rows with equal labels >= 0, in order of first appearance (vectorised: at Goku a Python loop over
+    the 1164 labels cost more than the device call)."""
+    labels = _index_array(labels, "the label array").reshape(-1)
+    if labels.shape[0] != n:
+        raise ValueError(f"leave_out: a label array needs one label per training row ({n}), got {labels.shape[0]}")
+    if labels.size and labels.min() < -1:
+        raise ValueError("leave_out: labels are >= 0, or -1 for a row that is never left out")
+    idx = np.flatnonzero(labels >= 0)
+    if idx.size == 0:
+        return np.zeros((1,), dtype=np.int32), np.zeros((0,), dtype=np.int32), 0
+    _, first, inv = np.unique(labels[idx], return_index=True, return_inverse=True)
+    rank = np.empty_like(first)
+    rank[np.argsort(first)] = np.arange(first.size)   # label -> its place by first appearance
+    gid = rank[inv.reshape(-1)]
+    sizes = np.bincount(gid)
+    if sizes.max() > MAX_GROUP:
+        k = int(np.argmax(sizes > MAX_GROUP))
+        raise _too_large(k, int(sizes[k]))
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    return offsets, idx[np.argsort(gid, kind="stable")].astype(np.int32), int(sizes.max())
+
+
+def _groups_from_lists(groups, n):
+    lists = []
+    for k, g in enumerate(groups):
+        a = _index_array(g, f"group {k}")
+        if a.ndim != 1:
+            raise ValueError(f"leave_out: group {k} is not a 1-D index array")
+        a = np.sort(a)
+        if a.size == 0:
+            raise ValueError(f"leave_out: group {k} is empty")
+        if a.size > MAX_GROUP:
+            raise _too_large(k, a.size)
+        if a[0] < 0 or a[-1] >= n:
+            raise ValueError(f"leave_out: group {k} holds an index outside 0..{n - 1}")
+        if np.any(a[1:] == a[:-1]):
+            raise ValueError(f"leave_out: group {k} lists a row twice")
+        lists.append(a)
+    if not lists:
+        return np.zeros((1,), dtype=np.int32), np.zeros((0,), dtype=np.int32), 0
+    sizes = np.array([a.size for a in lists], dtype=np.int64)
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    return offsets, np.concatenate(lists).astype(np.int32), int(sizes.max())
+
+
+def normalize_groups(groups, n: int):
+    """The three accepted forms of ``groups`` as ``(offsets [G + 1], rows [R], gmax)``, int32 host
+    arrays laid out as mfgp_gpr_posterior_leave_out reads them: group g is ``rows[offsets[g]:
+    offsets[g + 1]]``, ascending.  None: every one of the n rows is its own group.  A 1-D integer
+    array (or flat list) of n labels: rows with equal labels >= 0 form a group, in order of first
+    appearance; -1 keeps a row out of every group.  A sequence of index arrays (or a 2-D array, one
+    group a row): one group each; a row may appear in several groups.  ValueError for an empty group,
+    more than 32 rows in a group, a duplicate index inside a group or an index outside 0..n-1.  Pure
+    host code."""
+    n = int(n)
+    if groups is None:
+        return np.arange(n + 1, dtype=np.int32), np.arange(n, dtype=np.int32), 1 if n else 0
+    if isinstance(groups, torch.Tensor):
+        groups = groups.detach().cpu().numpy()
+    if isinstance(groups, np.ndarray) and groups.dtype != object:
+        flat = groups.ndim == 1
+    else:
+        flat = len(groups) > 0 and all(np.ndim(g) == 0 for g in groups)
+    return _groups_from_labels(groups, n) if flat else _groups_from_lists(groups, n)
+
+
+def groups_by_input(X, only_hf: bool = False) -> np.ndarray:
+    """Labels [N] that group the rows of X ([N, D + 1], fidelity in the last column) whose D input
+    columns are bit-identical, numbered in order of first appearance: the ``groups`` argument of
+    ``GPRPosterior.leave_out`` that leaves a high-fidelity simulation out together with the
+    low-fidelity runs at the same input.  only_hf: groups without a row of fidelity 1 get label -1
+    (never left out), the others are numbered in order of first appearance.  Host numpy code."""
+    X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
+    if X.ndim != 2 or X.shape[1] < 1:
+        raise ValueError("groups_by_input: X must be [N, D + 1]")
+    seen, raw = {}, np.empty((X.shape[0],), dtype=np.int64)
+    for i in range(X.shape[0]):
+        raw[i] = seen.setdefault(X[i, :-1].tobytes(), len(seen))
+    if not only_hf:
+        return raw
+    keep = np.zeros((len(seen),), dtype=bool)
+    keep[raw[X[:, -1] == 1.0]] = True
+    renum = np.full((len(seen),), -1, dtype=np.int64)
+    renum[keep] = np.arange(int(keep.sum()))
+    return renum[raw]
 
 
 class _PredictFn(torch.autograd.Function):
@@ -215,6 +329,63 @@ class GPRPosterior(_Posterior):
         if full_cov:
             return as_result(mean), as_result(cov[None].expand(p, -1, -1).contiguous())
         return as_result(mean), as_result(var[:, None].expand(-1, p).contiguous())
+
+    def leave_out(self, groups=None, full_cov: bool = False) -> LeaveOutResult:
+        """Leave-group-out cross-validation at the snapshot's hyper-parameters: for every group of
+        training rows, what a model built without those rows predicts for them (``predict_f`` of that
+        model at the rows' own inputs), in closed form from the cached factors (mfgp_gpr_posterior_leave_out:
+        no Gram, no factorization of K, no Xnew).  ``groups``: see ``normalize_groups`` (None: every row
+        on its own; a label array, e.g. ``groups_by_input(X, only_hf=True)``; a sequence of index
+        arrays of at most 32 rows).  Returns a ``LeaveOutResult``; ``cov`` only with ``full_cov``.
+        ``log_density`` is the joint density of the group's *observations* (the likelihood variance
+        included).  Like predict_f it is the snapshot's until update_cache().
+
+        Graph model: the joint covariance is the one the factorization reads (the lower triangle of K;
+        the kernel's 1e-6 jitter is part of K and stays in the covariance).  With an asymmetric
+        ``rho_LF`` a refit's ``predict_f`` at a row of LF source j >= 1 takes its cross-covariance from
+        the other triangle and is another model there; rows of source 0 and HF rows agree with it."""
+        if self._precompute_cache is PrecomputeCacheType.NOCACHE:
+            raise NotImplementedError("leave_out: a NOCACHE posterior has no cached factors; use a TENSOR or "
+                                      "VARIABLE cache")
+        eng = Engine.get(self.cache.device if self.cache is not None else None)
+        self._require_cache(eng)
+        n, p, d = self._shape
+        offsets, rows, gmax = normalize_groups(groups, n)   # every ValueError is raised before any launch
+        ng, nr = offsets.shape[0] - 1, rows.shape[0]
+        group = np.repeat(np.arange(ng, dtype=np.int64), np.diff(offsets))
+        pos = np.arange(nr, dtype=np.int64) - offsets[:-1].astype(np.int64)[group]   # place inside the group
+        f64 = dict(dtype=torch.float64, device=eng.device)
+        if ng == 0:
+            z = lambda *s: as_result(torch.zeros(s, **f64))
+            return LeaveOutResult(rows.astype(np.int64), group, z(0, p), z(0, p), z(0, p),
+                                  z(0, 0, 0) if full_cov else None)
+        idx = torch.from_numpy(np.concatenate([offsets, rows, pos.astype(np.int32)])).to(eng.device)
+        d_off, d_rows, d_pos = idx[:ng + 1], idx[ng + 1:ng + 1 + nr], idx[ng + 1 + nr:].long()
+        resid, cov = torch.empty((nr, p), **f64), torch.empty((nr, gmax), **f64)
+        logd = torch.empty((ng, p), **f64)
+        info = torch.empty((ng,), dtype=torch.int32, device=eng.device)
+        lib = eng.lib
+        ws = eng.workspace("post_lo", eng._size(lib.mfgp_gpr_posterior_leave_out_workspace_size, self._nlf, n, p, d,
+                                                ng, nr))
+        check(lib.mfgp_gpr_posterior_leave_out(eng.h, self._nlf, n, p, d, ptr(self.cache), self.cache.numel(), ng,
+                                               ptr(d_off), ptr(d_rows), nr, gmax, ptr(ws), ws.numel(), ptr(resid), p,
+                                               ptr(cov), gmax, ptr(logd), ptr(info)), "mfgp_gpr_posterior_leave_out")
+        Y = self.model._device_data()[2]   # the construction-time targets (they cannot be reassigned)
+        mean = Y.index_select(0, d_rows) - resid
+        var = cov.gather(1, d_pos[:, None]).expand(-1, p).contiguous()
+        full = None
+        if full_cov:   # [G, gmax, gmax]: row r of the call's cov is row pos[r] of its group's block
+            full = torch.zeros((ng, gmax, gmax), **f64)
+            full[torch.from_numpy(group).to(eng.device), d_pos] = cov
+        bad = info.cpu().numpy()   # the one host read of a device word
+        if np.any(bad < 0):
+            raise MFGPError("leave_out: the device rejected the group table")
+        if np.any(bad > 0):
+            g = int(np.flatnonzero(bad)[0])
+            raise CholeskyError(f"leave_out: the held-out precision of group {g} (rows {rows[offsets[g]:offsets[g + 1]]}) "
+                                f"is not positive definite (pivot {int(bad[g])})")
+        return LeaveOutResult(rows.astype(np.int64), group, as_result(mean), as_result(var), as_result(logd),
+                              None if full is None else as_result(full))
 
     def _marginal(self, Xnew):
         mean, var = self.predict_f(Xnew.detach())
