@@ -454,6 +454,46 @@ int mfgp_gpr_posterior_leave_out(mfgp_handle_t h, int nlf, int n, int p, int d, 
                                  size_t ws_bytes, double* resid, int ldr, double* cov, int ldc, double* logdens,
                                  int* info);
 
+/* Simulation design from a GPR cache, at the cache's hyper-parameters: how much one more observation at
+ * each candidate input lowers the posterior variance of f over a weighted reference set, in closed
+ * form from the cached factors (no refit), for nlf = 0 and nlf > 0 alike.
+ *   Xall    [(nref + ncand) x (d + 1)] (ldx): the reference rows, then the candidate rows.  The fidelity
+ *           column of a candidate says which simulation is run, that of a reference whose error is
+ *           bought down.
+ *   w       [nref] weights >= 0 (NULL: ones).
+ *   score   [ncand]: score[c] = sum_r w[r] C(r, c)^2 / (v(c) + s2), where C is the [ref, cand] block of
+ *           the cov that mfgp_gpr_posterior_predict returns for Xall (K(Xref, Xcand) - A_ref^T A_cand, the
+ *           kernel's entry function in that argument order, no jitter), v the marginal var of the
+ *           candidate and s2 the cached likelihood variance.  A row whose fidelity is no source of the
+ *           kernel has a zero kernel row: such a candidate scores exactly 0, such a reference adds
+ *           exactly 0.  The nref x ncand block is formed tile by tile on chip, never in memory.
+ *   E       [k x (nref + ncand)] (ldE; may be NULL when k = 0): the conditioning rows of the k candidates
+ *           already picked in this batch, as design_append wrote them; C and v are then those after
+ *           observing the picks: C - E_ref^T E_cand, v - colsum(E_cand^2).  k <= 32.
+ *   refresh 1: run the predict call's forward on Xall and keep A = L^{-1} K(X, Xall) and v in ws;
+ *           0: reuse them.  Between a refresh = 1 call and the refresh = 0 / design_append calls that
+ *           rely on it, ws must not be touched by anything else, and the geometry, the cache and Xall
+ *           must be the same.
+ *   design_append  writes row k (< 32) of E for the candidate pick[0] (a device int: the host reads no
+ *           device word inside a batch): e(x) = C'(x, c*) / sqrt(v'(c*) + s2) over the nref + ncand
+ *           stacked columns, primes meaning "after rows 0..k-1".  A candidate may be picked again (a
+ *           replicate).  An index outside 0..ncand-1 writes a zero row.  Needs a refresh = 1 score call first.
+ * One launch behind the forward's two (score), one launch (append), each after one memset of the arrival
+ * counters; fixed-order sums and no floating-point atomics (the same inputs give the same bits); nothing
+ * is allocated, the cache is only read.  A negative count, k > 32 (append: k > 31) or nlf outside
+ * 0..MFGP_MAX_LF: MFGP_ERR_ARG; a cache or workspace smaller than the *_size calls report:
+ * MFGP_ERR_WORKSPACE before any device work; ncand = 0 is a no-op, nref = 0 writes zeros.  qmax (<= 32):
+ * the largest k the workspace will be used with.  Use the cache at the tile size it was built for. */
+int mfgp_gpr_posterior_design_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int nref, int ncand,
+                                             int qmax, size_t* bytes);
+int mfgp_gpr_posterior_design_score(mfgp_handle_t h, int nlf, int n, int p, int d, const void* cache,
+                                    size_t cache_bytes, const double* Xall, int ldx, int nref, int ncand,
+                                    const double* w, const double* E, int ldE, int k, void* ws, size_t ws_bytes,
+                                    double* score, int refresh);
+int mfgp_gpr_posterior_design_append(mfgp_handle_t h, int nlf, int n, int p, int d, const void* cache,
+                                     size_t cache_bytes, const double* Xall, int ldx, int nref, int ncand, void* ws,
+                                     size_t ws_bytes, const int* pick, double* E, int ldE, int k);
+
 /* Diagnostic: one v_mfma_f64_16x16x4_f64 with A[i][k] = 4i+k+1, B[k][j] = 100k+j;
  * writes C (16x16 row-major, device). */
 int mfgp_selftest_mfma(mfgp_handle_t h, double* out);

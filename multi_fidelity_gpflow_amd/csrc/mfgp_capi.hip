@@ -844,13 +844,14 @@ static int post_chunk(int T, int Ts, int batch) { return (long)batch * T * Ts >=
 
 struct PostLayout {
     int Ts, nspad, chunk, ntask, ngrp;
-    double *Apart, *Bpart, *mpart, *vpart, *Am, *Kss, *Cov;   // GPR
+    double *Apart, *Bpart, *mpart, *vpart, *Am, *Kss, *Cov;   // GPR; Kss / Cov are null with cov = false
+                                                              // (design: launch_post full = 0 never touches them)
     double *pa, *pb, *pm, *gm, *gv;                           // SVGP
     int* cnt;
     size_t bytes;
 };
 // svgp: batch = latents, T = Tm; gpr: batch = 1
-static PostLayout post_layout(int nb, int T, int Tp, int nstar, int batch, bool svgp, void* ws) {
+static PostLayout post_layout(int nb, int T, int Tp, int nstar, int batch, bool svgp, void* ws, bool cov = true) {
     PostLayout P{};
     P.Ts = ceil_div(nstar > 0 ? nstar : 1, nb);
     P.nspad = P.Ts * nb;
@@ -873,8 +874,10 @@ static PostLayout post_layout(int nb, int T, int Tp, int nstar, int batch, bool 
         P.mpart = c.take<double>((size_t)P.ngrp * P.nspad * Tp * nb);
         P.vpart = c.take<double>((size_t)P.ngrp * P.nspad);
         P.Am = c.take<double>((size_t)T * nb * P.nspad);
-        P.Kss = c.take<double>((size_t)P.nspad * P.nspad);
-        P.Cov = c.take<double>((size_t)P.nspad * P.nspad);
+        if (cov) {   // (the design calls keep A but never form a covariance block)
+            P.Kss = c.take<double>((size_t)P.nspad * P.nspad);
+            P.Cov = c.take<double>((size_t)P.nspad * P.nspad);
+        }
     }
     P.bytes = c.off + 256;
     return P;
@@ -1006,6 +1009,84 @@ static LoLayout lo_layout(int n, int p, int ngroups, int nrows, int gmax, void* 
     L.part = c.take<double>((size_t)L.ntmax * L.nch * L.ny * 32 * 32 * (1 + LO_PT));
     L.bytes = c.off + 256;
     return L;
+}
+
+// Design workspace: the counters first (one memset per call zeroes exactly that block), then the
+// predict layout of the nref + ncand stacked points without its covariance blocks (A is kept there),
+// then the forward's outputs (the mean is formed and not used: the forward is the predict call's own)
+// and the two kernels' partials.
+struct DesignLayout {
+    PostLayout P;
+    int nall, Tr, Tc, nrun, ncb, nrch;
+    int* cnt;            // [Tc] k_design_score, then [ncb] k_design_row
+    size_t cnt_bytes;
+    double *mean, *var, *dpart, *rpart;
+    size_t bytes;
+};
+static DesignLayout design_layout(int nb, int T, int Tp, int p, int nref, int ncand, void* ws) {
+    DesignLayout L{};
+    L.nall = nref + ncand;
+    L.Tr = ceil_div(nref > 0 ? nref : 1, nb);
+    L.Tc = ceil_div(ncand > 0 ? ncand : 1, nb);
+    L.nrun = ceil_div(L.Tr, design_run(nb));
+    L.ncb = ceil_div(L.nall > 0 ? L.nall : 1, NTHREADS);
+    L.nrch = ceil_div(T * nb, DESIGN_RROWS);
+    Carve c(ws);
+    L.cnt_bytes = (sizeof(int) * ((size_t)L.Tc + L.ncb) + 15) & ~(size_t)15;
+    L.cnt = c.take<int>(L.cnt_bytes / sizeof(int));
+    const size_t o = (c.off + 255) & ~(size_t)255;
+    L.P = post_layout(nb, T, Tp, L.nall, 1, false, ws ? (char*)ws + o : nullptr, false);
+    const size_t pb = (L.P.bytes + 255) & ~(size_t)255;
+    Carve c2(ws ? (char*)ws + o + pb : nullptr);
+    L.mean = c2.take<double>((size_t)L.nall * p);
+    L.var = c2.take<double>((size_t)L.nall);
+    L.dpart = c2.take<double>((size_t)L.nrun * L.Tc * nb);
+    L.rpart = c2.take<double>((size_t)L.nrch * L.ncb * NTHREADS);
+    L.bytes = o + pb + c2.off + 256;
+    return L;
+}
+
+// mode 0: score (refresh: the forward first); mode 1: append row k of E for the picked candidate
+template <int NB>
+static int gpr_posterior_design_impl(mfgp_handle_t h, int nlf, int n, int p, int d, const void* cache,
+                                     size_t cache_bytes, const double* Xall, int ldx, int nref, int ncand,
+                                     const double* w, double* E, int ldE, int k, void* ws, size_t ws_bytes,
+                                     double* score, int refresh, const int* pick) {
+    const GprCache c = gpr_cache_layout(NB, nlf, n, p, d, const_cast<void*>(cache));
+    const DesignLayout L = design_layout(NB, c.T, c.Tp, p, nref, ncand, ws);
+    if (cache_bytes < c.bytes || ws_bytes < L.bytes) return MFGP_ERR_WORKSPACE;
+    hipStream_t s = h->stream;
+    if (!pick && refresh) {
+        PostArgs a{};
+        a.Li = c.LZ; a.ldl = c.ldr; a.sL = 0;
+        a.X1 = c.X; a.ldx1 = d + 1; a.n1 = n;
+        a.theta = c.theta; a.stheta = 0;
+        a.Xs = Xall; a.ldxs = ldx; a.nstar = L.nall;
+        a.D = d; a.nlf = nlf;
+        a.T = c.T; a.Ts = L.P.Ts; a.chunk = L.P.chunk; a.full = 0; a.ntask = L.P.ntask; a.ngrp = L.P.ngrp;
+        a.Apart = L.P.Apart; a.cnt = L.P.cnt;
+        a.Zc = c.LZ + c.npad; a.ldz = c.ldr; a.Tp = c.Tp; a.p = p;
+        a.Am = L.P.Am; a.ldam = L.P.nspad;
+        a.mpart = L.P.mpart; a.vpart = L.P.vpart;
+        a.mean = L.mean; a.ldm = p; a.var = L.var;
+        launch_post<NB>(a, 1, s);
+    }
+    (void)hipMemsetAsync(L.cnt, 0, L.cnt_bytes, s);
+    DesignArgs g{};
+    g.Am = L.P.Am; g.ldam = L.P.nspad; g.npad = c.npad;
+    g.var = L.var;
+    g.Xall = Xall; g.ldx = ldx; g.nref = nref; g.ncand = ncand;
+    g.theta = c.theta; g.noise = c.theta + c.G - 1;   // the likelihood variance closes both theta layouts
+    g.D = d; g.nlf = nlf;
+    g.w = w;
+    g.E = E; g.ldE = ldE; g.k = k;
+    g.T = c.T; g.Tr = L.Tr; g.Tc = L.Tc; g.nrun = L.nrun;
+    g.dpart = L.dpart; g.dcnt = L.cnt; g.score = score;
+    g.pick = pick; g.Erow = pick ? E + (size_t)k * ldE : nullptr;
+    g.ncb = L.ncb; g.nrch = L.nrch; g.rpart = L.rpart; g.rcnt = L.cnt + L.Tc;
+    if (pick) launch_design_row(g, s);
+    else launch_design_score<NB>(g, s);
+    return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
 }
 
 // SVGP cache: [Z: m x (d + 1)][thetas: l x G][W: p x l][q_mu^T: l x Mpad, zero padded]
@@ -1855,6 +1936,60 @@ int mfgp_gpr_posterior_leave_out(mfgp_handle_t h, int nlf, int n, int p, int d, 
     a.resid = resid; a.ldres = ldr; a.cov = cov; a.ldc = ldc; a.logdens = logdens; a.info = info;
     launch_leave_out(a, h->stream);
     return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
+}
+
+static bool design_geometry_ok(int nlf, int n, int p, int nref, int ncand) {
+    return nlf >= 0 && nlf <= MFGP_MAX_LF && n >= 1 && p >= 1 && nref >= 0 && ncand >= 0 &&
+           (long)nref + ncand <= 0x7fffffffL - 4096;
+}
+
+int mfgp_gpr_posterior_design_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int nref, int ncand,
+                                             int qmax, size_t* bytes) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (!design_geometry_ok(nlf, n, p, nref, ncand) || qmax < 0 || qmax > DESIGN_MAXQ || !bytes) return MFGP_ERR_ARG;
+    const GprCache c = gpr_cache_layout(h->nb, nlf, n, p, d, nullptr);
+    *bytes = design_layout(h->nb, c.T, c.Tp, p, nref, ncand, nullptr).bytes;
+    return MFGP_OK;
+}
+
+int mfgp_gpr_posterior_design_score(mfgp_handle_t h, int nlf, int n, int p, int d, const void* cache,
+                                    size_t cache_bytes, const double* Xall, int ldx, int nref, int ncand,
+                                    const double* w, const double* E, int ldE, int k, void* ws, size_t ws_bytes,
+                                    double* score, int refresh) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (!design_geometry_ok(nlf, n, p, nref, ncand) || k < 0 || k > DESIGN_MAXQ) return MFGP_ERR_ARG;
+    if (ncand == 0) return MFGP_OK;
+    if (!cache || !Xall || !ws || !score || ldx < d + 1 || (k > 0 && (!E || ldE < nref + ncand))) return MFGP_ERR_ARG;
+    if (nref == 0) {   // nothing to buy down: zeros, after the same size checks as any other call
+        const GprCache c = gpr_cache_layout(h->nb, nlf, n, p, d, nullptr);
+        if (cache_bytes < c.bytes || ws_bytes < design_layout(h->nb, c.T, c.Tp, p, nref, ncand, nullptr).bytes)
+            return MFGP_ERR_WORKSPACE;
+        (void)hipMemsetAsync(score, 0, sizeof(double) * (size_t)ncand, h->stream);
+        return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
+    }
+    double* Em = const_cast<double*>(E);   // (only read in this mode)
+    if (h->nb == 64)
+        return gpr_posterior_design_impl<64>(h, nlf, n, p, d, cache, cache_bytes, Xall, ldx, nref, ncand, w, Em, ldE,
+                                             k, ws, ws_bytes, score, refresh, nullptr);
+    return gpr_posterior_design_impl<32>(h, nlf, n, p, d, cache, cache_bytes, Xall, ldx, nref, ncand, w, Em, ldE, k, ws,
+                                         ws_bytes, score, refresh, nullptr);
+}
+
+int mfgp_gpr_posterior_design_append(mfgp_handle_t h, int nlf, int n, int p, int d, const void* cache,
+                                     size_t cache_bytes, const double* Xall, int ldx, int nref, int ncand, void* ws,
+                                     size_t ws_bytes, const int* pick, double* E, int ldE, int k) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (!design_geometry_ok(nlf, n, p, nref, ncand) || k < 0 || k >= DESIGN_MAXQ) return MFGP_ERR_ARG;
+    if (ncand == 0) return MFGP_OK;
+    if (!cache || !Xall || !ws || !pick || !E || ldx < d + 1 || ldE < nref + ncand) return MFGP_ERR_ARG;
+    if (h->nb == 64)
+        return gpr_posterior_design_impl<64>(h, nlf, n, p, d, cache, cache_bytes, Xall, ldx, nref, ncand, nullptr, E,
+                                             ldE, k, ws, ws_bytes, nullptr, 0, pick);
+    return gpr_posterior_design_impl<32>(h, nlf, n, p, d, cache, cache_bytes, Xall, ldx, nref, ncand, nullptr, E, ldE, k,
+                                         ws, ws_bytes, nullptr, 0, pick);
 }
 
 int mfgp_svgp_posterior_size(mfgp_handle_t h, int m, int l, int p, int d, size_t* bytes) {

@@ -241,6 +241,36 @@ struct LoArgs {
 };
 void launch_leave_out(const LoArgs& a, hipStream_t s);
 
+// Simulation design from the GPR cache (mfgp_design.hip).  The forward (launch_post, A kept) has run on
+// the stacked points [Xref ; Xcand]; k_design_score forms C = K(Xref, Xcand) - A_ref^T A_cand -
+// E_ref^T E_cand tile pair by tile pair in LDS and reduces sum_r w_r C(r, c)^2 / (v'(c) + s2);
+// k_design_row appends the conditioning row of one picked candidate to E.
+constexpr int DESIGN_MAXQ = 32;      // rows of E (picks a batch conditions on)
+constexpr int DESIGN_RROWS = 128;    // rows of A one k_design_row workgroup takes
+constexpr int design_run(int nb) { return nb == 32 ? 4 : 2; }   // reference row tiles per k_design_score task (128 rows)
+struct DesignArgs {
+    const double* Am; long ldam; int npad;    // A = L^{-1} K(X, [Xref ; Xcand]), npad x nspad (kept by the forward)
+    const double* var;                        // [nref + ncand] marginal variances (the forward's)
+    const double* Xall; long ldx;             // stacked inputs [nref + ncand, D + 1]
+    int nref, ncand;
+    const double* theta; const double* noise; // cached kernel parameters; their last entry, the likelihood variance
+    int D, nlf;
+    const double* w;                          // [nref] reference weights; nullptr: ones
+    const double* E; long ldE; int k;         // k conditioning rows over the stacked columns
+    int T, Tr, Tc, nrun;                      // row tiles of A, reference / candidate tiles, ceil(Tr / design_run)
+    double* dpart;                            // [nrun][Tc * NB] partial column sums
+    int* dcnt;                                // [Tc] arrival counters (zero on entry)
+    double* score;                            // [ncand]
+    // k_design_row: row k of E = C'(x, c*) / sqrt(v'(c*) + s2) over the stacked columns x
+    const int* pick;                          // device: the picked candidate (outside 0..ncand-1: a zero row)
+    double* Erow;                             // E + k ldE
+    int ncb, nrch;                            // blocks of NTHREADS columns, chunks of DESIGN_RROWS rows
+    double* rpart;                            // [nrch][ncb * NTHREADS] partial products
+    int* rcnt;                                // [ncb] arrival counters (zero on entry)
+};
+template <int NB> void launch_design_score(const DesignArgs& a, hipStream_t s);
+void launch_design_row(const DesignArgs& a, hipStream_t s);
+
 // tril(q_sqrt) zero padded / C = Lq^T Linv of the SVGP K_uu pipeline, into caller buffers (mfgp_svgp.hip)
 int svgp_posterior_factor(hipStream_t s, int nb, int m, int l, int d, const double* Z, int ldz, const double* thetas,
                           const double* q_sqrt, double jitter, void* ws, size_t ws_bytes, double* Li, double* C,

@@ -18,12 +18,9 @@
 // loads (st_coherent / ld_coherent), the producer drains its stores before the arrival atomic.
 #include "mfgp_device.h"
 #include "mfgp_internal.h"
+#include "mfgp_post_device.h"
 
 namespace mfgp {
-
-constexpr int PMAXD = 32;
-constexpr int PXS = PMAXD + 1;   // LDS row stride of staged inputs (odd: distinct banks over rows)
-constexpr int PTHETA = 192;      // theta entries staged in LDS (graph kernel, 4 sources, D = 32: 186)
 
 int post_ntasks(int T, int chunk, int full) {
     int n = 0;
@@ -36,100 +33,6 @@ __device__ __forceinline__ void post_row_tasks(int T, int chunk, int full, int i
     base = 0;
     for (int j = 0; j < i; ++j) base += ((full ? T : j + 1) + chunk - 1) / chunk;
     nch = ((full ? T : i + 1) + chunk - 1) / chunk;
-}
-
-// The NB x NB tile K(x1 rows, xs rows) of the linear multi-fidelity kernel into Ks.  A thread owns
-// column c = t % NB of rows t / NB + (NTHREADS / NB) q and works on four of its entries at a time:
-// the four distance sums share the column's reads and run as independent chains, the exponentials
-// go through exp4.  A product workgroup is often alone on its CU (one wave per SIMD, nothing to
-// hide a latency behind), where the entry-at-a-time form left every LDS read and every step of the
-// exp polynomial exposed.  Exact == 0 / == 1 fidelity masks (anything else: a zero row / column,
-// linear.py:67-70); r^2 in direct-difference form, il = [1 / lL | 1 / lD].
-template <int NB>
-__device__ __forceinline__ void post_mf_tile(double* Ks, const double* x1, const double* f1, const double* xs,
-                                             const double* fs, int D, const double* il, const double* th) {
-    constexpr int S = TileCfg<NB>::S;
-    constexpr int RSTEP = NTHREADS / NB;           // rows between a thread's consecutive entries
-    constexpr int NE = NB * NB / NTHREADS;         // entries per thread (a multiple of 4)
-    const int t = threadIdx.x, c = t % NB, rb = t / NB;
-    const double* xb = xs + c * PXS;
-    const double fb = fs[c];
-    const bool Lb = (fb == 0.0), Hb = (fb == 1.0);
-    const double vL = th[0], vD = th[1 + D], rho = th[2 + 2 * D];
-    for (int g = 0; g < NE; g += 4) {
-        const int r0 = rb + g * RSTEP;
-        const double* xa = x1 + r0 * PXS;
-        double kl[4] = {0.0, 0.0, 0.0, 0.0}, kd[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int d = 0; d < D; ++d) {
-            const double b = xb[d], lL = il[d], lD = il[PMAXD + d];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const double df = xa[j * RSTEP * PXS + d] - b;
-                const double qL = df * lL, qD = df * lD;
-                kl[j] += qL * qL;
-                kd[j] += qD * qD;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { kl[j] *= -0.5; kd[j] *= -0.5; }
-        exp4(kl);
-        exp4(kd);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const double fa = f1[r0 + j * RSTEP];
-            const bool La = (fa == 0.0), Ha = (fa == 1.0);
-            const double kL = vL * kl[j];
-            double v = (La && Lb) ? kL : (!(Ha && Hb) ? kL * rho : kL * (rho * rho) + vD * kd[j]);
-            if (!(La || Ha) || !(Lb || Hb)) v = 0.0;
-            Ks[(r0 + j * RSTEP) * S + c] = v;
-        }
-    }
-}
-
-// K_diag of one X* row (k_kdiag's expressions)
-__device__ __forceinline__ double post_kdiag(double f, const double* theta, int D, int nlf) {
-    if (nlf) {
-        const GraphTheta th{theta, D, nlf};
-        const int s = graph_source(f, nlf);
-        double v = 0.0;
-        if (s >= 0 && s < nlf) v = th.v(s);
-        else if (s == nlf) {
-            for (int k = 0; k < nlf; ++k) v += th.v(k) * (th.rho(k) * th.rho(k));
-            v += th.v(nlf);
-        }
-        return v;
-    }
-    const MFTheta th{theta, D};
-    const double rho = th.rho();
-    return (f == 0.0) ? th.vL() : ((f == 1.0) ? th.vL() * (rho * rho) + th.vD() : 0.0);
-}
-
-// sum over k < n of base[k * stride] in k order; the sc1 loads are issued eight at a time (one at a
-// time, a thread's sum cost a memory round trip per term; W = 32 for k_post_grad's long task lists)
-template <int W = 8>
-__device__ __forceinline__ double post_sum_coherent(const double* base, long stride, int n) {
-    double s = 0.0;
-    for (int k0 = 0; k0 < n; k0 += W) {
-        double v[W];
-#pragma unroll
-        for (int j = 0; j < W; ++j) v[j] = k0 + j < n ? ld_coherent(base + (long)(k0 + j) * stride) : 0.0;
-#pragma unroll
-        for (int j = 0; j < W; ++j) s += v[j];
-    }
-    return s;
-}
-
-// the same for data of an earlier launch (plain loads)
-__device__ __forceinline__ double post_sum(const double* base, long stride, int n) {
-    double s = 0.0;
-    for (int k0 = 0; k0 < n; k0 += 8) {
-        double v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = k0 + j < n ? base[(long)(k0 + j) * stride] : 0.0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s += v[j];
-    }
-    return s;
 }
 
 template <int NB>

@@ -15,6 +15,11 @@ vector-Jacobian product with respect to ``Xnew`` from one call (``mfgp_*_posteri
 predict call's two launches and one more), and the cached marginal ``predict_f`` of a torch ``Xnew``
 with ``requires_grad=True`` is attached to autograd through it.  The fidelity column of ``Xnew``
 enters the kernels only through exact ``== 0`` / ``== 1`` tests, so its gradient is exactly zero.
+
+Simulation design: ``GPRPosterior.variance_reduction(Xcand, Xref, weights)`` scores every candidate run by
+the posterior variance it buys down over a reference set, and ``GPRPosterior.select`` picks a greedy batch
+by ``argmax(score / cost)``, both in closed form from the cached factors (``mfgp_gpr_posterior_design_score``
+/ ``_append``: the reference x candidate covariance block is formed on chip, never in memory).
 """
 from __future__ import annotations
 
@@ -74,6 +79,39 @@ class LeaveOutResult(NamedTuple):
     var: torch.Tensor           # [R, P] marginal variance of f, tiled over P as predict_f tiles it
     log_density: torch.Tensor   # [G, P] joint log predictive density of each group's observations
     cov: Optional[torch.Tensor] = None   # [G, gmax, gmax] covariance of f_S, zero outside each group's block
+
+
+MAX_BATCH = 32   # picks of one greedy batch (include/mfgp.h mfgp_gpr_posterior_design_score: k <= 32)
+
+
+class DesignResult(NamedTuple):
+    """What ``GPRPosterior.select`` returns: the greedy batch, pick after pick (device tensors)."""
+    picks: torch.Tensor   # int64 [q] rows of Xcand, in the order they were picked (a row may repeat)
+    gain: torch.Tensor    # [q] the score (not divided by the cost) of each pick at its step
+
+
+def _design_rows(X, d, what):
+    """Row count of an [N, d + 1] input (numpy / list / torch), ValueError otherwise; host only."""
+    shape = tuple(X.shape) if isinstance(X, torch.Tensor) else np.shape(X)
+    if len(shape) != 2 or shape[1] != d + 1:
+        raise ValueError(f"{what} has shape {shape}, expected [N, {d + 1}] (D inputs and the fidelity column)")
+    return int(shape[0])
+
+
+def _design_vector(v, n, what, positive):
+    """weights (>= 0) / cost (> 0) as a float64 tensor of n entries where it lives, checked before any
+    device work of the call (for a device tensor that check is the call's one host read)."""
+    if v is None:
+        return None
+    if isinstance(v, torch.Tensor):
+        t = v.detach().to(torch.float64)
+    else:
+        t = torch.as_tensor(np.asarray(v, dtype=np.float64))
+    if tuple(t.shape) != (n,):
+        raise ValueError(f"{what} has shape {tuple(t.shape)}, expected ({n},)")
+    if not bool(((t > 0) if positive else (t >= 0)).all()):
+        raise ValueError(f"{what} must be {'positive' if positive else 'non-negative'} (and not NaN)")
+    return t
 
 
 def _index_array(g, what):
@@ -386,6 +424,86 @@ class GPRPosterior(_Posterior):
                                 f"is not positive definite (pivot {int(bad[g])})")
         return LeaveOutResult(rows.astype(np.int64), group, as_result(mean), as_result(var), as_result(logd),
                               None if full is None else as_result(full))
+
+    def variance_reduction(self, Xcand, Xref, weights=None):
+        """How much one more simulation at each candidate lowers the posterior variance of f over a
+        reference set, at the snapshot's hyper-parameters (the ALC / integrated-variance criterion):
+        ``score[c] = sum_r weights[r] cov(f(Xref_r), f(Xcand_c))^2 / (var f(Xcand_c) + s2)``, shape [Nc].
+        Xcand [Nc, D + 1] and Xref [Nr, D + 1] carry the fidelity in the last column: the candidate's says
+        which simulation is run, the reference's whose error is bought down.  ``weights`` [Nr] >= 0
+        (None: ones).  cov and var are those of ``predict_f(vstack(Xref, Xcand), full_cov=True)``, s2 the
+        likelihood variance; the variance is shared by the P outputs, so there is no P axis.  The
+        Nr x Nc block is formed on chip by one fused kernel (mfgp_gpr_posterior_design_score), never in
+        memory.  A row whose fidelity is no source of the kernel scores / adds exactly 0.  Like
+        predict_f it is the snapshot's until update_cache().
+
+        Graph model: the block is the one full_cov returns (the kernel's entry function with the
+        reference as its row).  With an asymmetric ``rho_LF`` its reading as "the variance after a refit"
+        holds only at references of LF source 0 and HF references (see ``leave_out``)."""
+        return self._design(Xcand, Xref, weights, None, None, "variance_reduction")
+
+    def select(self, Xcand, Xref, q, weights=None, cost=None) -> DesignResult:
+        """A greedy batch of q simulations (q <= 32): each step takes ``argmax(score / cost)`` of
+        ``variance_reduction`` (the lowest index wins a tie), then conditions every later covariance on
+        the pick, in closed form (one more row under the cached A: mfgp_gpr_posterior_design_append).
+        ``cost`` [Nc] > 0 (None: ones), e.g. 1 for an LF and 4 for an HF run.  A candidate may be picked
+        again: a replicate is a legitimate design.  Returns ``DesignResult(picks, gain)``; ``gain[k]`` is
+        the score (not divided by the cost) of pick k at its step.  After the argument checks the whole
+        batch is enqueued without a host read of a device word: the pick is copied and its score gathered
+        on the device."""
+        return self._design(Xcand, Xref, weights, cost, q, "select")
+
+    def _design(self, Xcand, Xref, weights, cost, q, what):
+        if self._precompute_cache is PrecomputeCacheType.NOCACHE:
+            raise NotImplementedError(f"{what}: a NOCACHE posterior has no cached factors; use a TENSOR or "
+                                      "VARIABLE cache")
+        n, p, d = self._shape
+        nc, nr = _design_rows(Xcand, d, f"{what}: Xcand"), _design_rows(Xref, d, f"{what}: Xref")
+        w = _design_vector(weights, nr, f"{what}: weights", False)
+        cost = _design_vector(cost, nc, f"{what}: cost", True)
+        if q is not None:
+            if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or q < 1 or q > MAX_BATCH:
+                raise ValueError(f"{what}: q must be an integer in 1..{MAX_BATCH}, got {q!r}")
+            if nc == 0:
+                raise ValueError(f"{what}: no candidate to pick from (Xcand has no rows)")
+            q = int(q)
+        eng = Engine.get(self.cache.device if self.cache is not None else None)   # every ValueError is raised above
+        self._require_cache(eng)
+        f64 = dict(dtype=torch.float64, device=eng.device)
+        if cost is not None:
+            cost = cost.to(eng.device)
+        if nc == 0 or nr == 0:   # nothing to score / nothing to buy down: zeros, no launch
+            score = torch.zeros((nc,), **f64)
+            if q is None:
+                return as_result(score)
+            idx = torch.argmax(score if cost is None else score / cost)
+            return DesignResult(as_result(idx.repeat(q)), as_result(torch.zeros((q,), **f64)))
+        Xall = torch.cat([to_dev(Xref, eng.device), to_dev(Xcand, eng.device)]).contiguous()
+        w = None if w is None else w.to(eng.device).contiguous()
+        nall, steps = nr + nc, 1 if q is None else q
+        lib, nlf = eng.lib, self._nlf
+        ws = eng.workspace("post_design", eng._size(lib.mfgp_gpr_posterior_design_workspace_size, nlf, n, p, d, nr, nc,
+                                                    steps))
+        E = torch.empty((steps - 1, nall), **f64) if steps > 1 else None
+        picks = torch.empty((steps,), dtype=torch.int64, device=eng.device)
+        gain = torch.empty((steps,), **f64)
+        for k in range(steps):
+            score = torch.empty((nc,), **f64)
+            check(lib.mfgp_gpr_posterior_design_score(eng.h, nlf, n, p, d, ptr(self.cache), self.cache.numel(),
+                                                      ptr(Xall), d + 1, nr, nc, ptr(w), ptr(E), nall, k, ptr(ws),
+                                                      ws.numel(), ptr(score), 1 if k == 0 else 0),
+                  "mfgp_gpr_posterior_design_score")
+            if q is None:
+                return as_result(score)
+            idx = torch.argmax(score if cost is None else score / cost)
+            picks[k] = idx
+            gain[k:k + 1] = score.index_select(0, idx.reshape(1))   # score[idx] would read idx on the host
+            if k + 1 < steps:
+                pick = idx.to(torch.int32)
+                check(lib.mfgp_gpr_posterior_design_append(eng.h, nlf, n, p, d, ptr(self.cache), self.cache.numel(),
+                                                           ptr(Xall), d + 1, nr, nc, ptr(ws), ws.numel(), ptr(pick),
+                                                           ptr(E), nall, k), "mfgp_gpr_posterior_design_append")
+        return DesignResult(as_result(picks), as_result(gain))
 
     def _marginal(self, Xnew):
         mean, var = self.predict_f(Xnew.detach())

@@ -1,0 +1,123 @@
+"""Per-call time of simulation design from the cached GPR posterior (GPRPosterior.variance_reduction /
+select) against the routes that give the same numbers without it.
+
+  MultiFidelityGPModel at Goku (N = 1164, P = 64, D = 10), tile 32, the initial parameters;
+  Nr = 1024 HF references, Nc = 2048 candidates (1024 seeded inputs at both fidelities), all on the device.
+
+Variants:
+  fused            post.variance_reduction(Xcand, Xref): the forward on the stacked points and k_design_score
+  full_cov_c       the C call mfgp_gpr_posterior_predict with cov on the stacked points (writes the
+                   (Nr + Nc)^2 block) and the torch reduction of its [ref, cand] block and diagonal
+  full_cov         the same through post.predict_f(Xall, full_cov=True), which also tiles the block over P
+  select8          post.select(Xcand, Xref, 8, cost = 1 LF / 4 HF)
+  select8_full_cov the full_cov_c block once, then 8 rounds of score, argmax and a rank-one downdate of the
+                   whole block in torch: conditioning without a refit, by what the library offered before
+
+Method as tools/bench_posterior.py: every variant warmed; a window is a host clock around `--calls` calls
+that ends in a device synchronise; the variants alternate window by window in one process; median with
+min / max over `--windows` windows.  Prints one JSON line (and writes it to --out).
+GPU box: python tools/bench_design.py --out profiles/design/bench.json
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from multi_fidelity_gpflow_amd._lib import check, ptr   # noqa: E402
+from multi_fidelity_gpflow_amd.engine import Engine   # noqa: E402
+from oracle.mfgp_oracle import load_powerspecs   # noqa: E402
+from bench_leave_out import initial_model   # noqa: E402
+from bench_posterior import GOKU_DIR, measure   # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=20, help="calls per timed window")
+    ap.add_argument("--windows", type=int, default=7, help="windows per variant (alternating)")
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--nref", type=int, default=1024)
+    ap.add_argument("--ninputs", type=int, default=1024, help="candidate inputs (each at both fidelities)")
+    ap.add_argument("--q", type=int, default=8)
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    a = ap.parse_args()
+    eng = Engine.get()
+    eng.set_tile(32)
+    d = load_powerspecs(GOKU_DIR)
+    X, Y = d["X"], d["Y"]
+    n, p, D = X.shape[0], Y.shape[1], X.shape[1] - 1
+    model = initial_model(X, Y)
+    post = model.posterior()
+    s2 = float(model.likelihood.variance.numpy())
+    rng = np.random.default_rng(2048)
+    nr, ni = a.nref, a.ninputs
+    nc = 2 * ni
+    xin = rng.random((ni, D))
+    dev = lambda v: torch.tensor(np.ascontiguousarray(v), device=eng.device)
+    Xref = dev(np.hstack([rng.random((nr, D)), np.ones((nr, 1))]))
+    Xcand = dev(np.vstack([np.hstack([xin, np.zeros((ni, 1))]), np.hstack([xin, np.ones((ni, 1))])]))
+    cost = dev(np.where(np.arange(nc) < ni, 1.0, 4.0))
+    Xall = torch.cat([Xref, Xcand]).contiguous()
+    nall = nr + nc
+    f64 = dict(dtype=torch.float64, device=eng.device)
+    lib = eng.lib
+    mean, var, cov = torch.empty((nall, p), **f64), torch.empty((nall,), **f64), torch.empty((nall, nall), **f64)
+
+    def block():
+        ws = eng.workspace("post_pred", eng._size(lib.mfgp_gpr_posterior_predict_workspace_size, 0, n, p, D, nall))
+        check(lib.mfgp_gpr_posterior_predict(eng.h, 0, n, p, D, nall, ptr(post.cache), post.cache.numel(), ptr(Xall),
+                                             D + 1, ptr(ws), ws.numel(), ptr(mean), p, ptr(var), ptr(cov), nall),
+              "mfgp_gpr_posterior_predict")
+        return cov
+
+    def reduce(S):
+        C = S[:nr, nr:]
+        return (C * C).sum(dim=0) / (torch.diagonal(S)[nr:] + s2)
+
+    def full_cov_c():
+        return reduce(block())
+
+    def full_cov():
+        return reduce(post.predict_f(Xall, full_cov=True)[1][0])
+
+    def select_full_cov():
+        S = block()
+        picks = torch.empty((a.q,), dtype=torch.int64, device=eng.device)
+        for k in range(a.q):
+            c = nr + torch.argmax(reduce(S) / cost)
+            picks[k] = c - nr
+            col = S.index_select(1, c.reshape(1))
+            S -= (col / (col.index_select(0, c.reshape(1)) + s2)) @ S.index_select(0, c.reshape(1))
+        return picks
+
+    fused = lambda: post.variance_reduction(Xcand, Xref)
+    select = lambda: post.select(Xcand, Xref, a.q, cost=cost)
+    ref = full_cov_c()
+    agree = float(((fused() - ref).abs().max() / ref.abs().max()).item())
+    same_picks = select().picks.tolist() == select_full_cov().tolist()
+    out = dict(bench="design", device=torch.cuda.get_device_name(eng.index), calls=a.calls, windows=a.windows,
+               tile=eng.tile(), n=int(n), p=int(p), nref=nr, ncand=nc, q=a.q,
+               unit="us per call (host clock, window ends in a device synchronise)",
+               fused_vs_full_cov_rel_diff=agree, select_picks_equal_full_cov_route=bool(same_picks),
+               block_bytes=int(nall) * int(nall) * 8)
+    r = measure({"fused": fused, "full_cov_c": full_cov_c, "full_cov": full_cov, "select8": select,
+                 "select8_full_cov": select_full_cov}, a.calls, a.windows, a.warmup)
+    out.update(r)
+    out["fused_over_full_cov_c"] = round(r["fused"]["median_us"] / r["full_cov_c"]["median_us"], 4)
+    out["fused_over_full_cov"] = round(r["fused"]["median_us"] / r["full_cov"]["median_us"], 4)
+    out["select8_over_full_cov_route"] = round(r["select8"]["median_us"] / r["select8_full_cov"]["median_us"], 4)
+    line = json.dumps(out)
+    print(line, flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
