@@ -17,37 +17,9 @@
 #include <mutex>
 #include <thread>
 
-#include "../../include/mfgp.h"
 #include "mfgp_device.h"
-#include "mfgp_internal.h"
+#include "mfgp_host.h"
 #include "mfgp_flow.h"
-
-struct mfgp_handle_s {
-    int device;
-    hipStream_t stream;
-    int nb;
-    int grad_chunk;
-    int flow_wgs;   // k_chol_flow grid (one workgroup per CU); 0: launch-per-step Cholesky
-    int flow_min_t; // fewest 32-tiles a factorization needs to take the flow (below: the step launches)
-    int ncu;        // compute units of the device
-    int gram_wgs;   // k_gram tile workgroups, LML layout (0: one per CU; < 0: one per tile; MFGP_GRAM_WGS)
-    int flow_trace; // k_chol_flow writes its diagnostic timeline into the workspace
-    long long flow_timeout;   // k_chol_flow hand-off wait bound (100 MHz ticks)
-    int f32_panel;  // fp32 path: 128-wide tile columns per outer panel (trailing-update K = 128 * f32_panel)
-    int f32_lookahead;          // fp32 sweep: factor the next panel beside the trailing update
-    int f32_reserve;            // CUs the capped trailing update leaves to the side stream
-    int f32_refine;             // fp32 value-only LML (one step) / predict mean (this many steps): fp64 refinement (mfgp_set_f32_refine)
-    int tiny;                   // small problems (n, p <= 64, D <= 16, AR1 kernel): one-launch LML step (default on; MFGP_TINY=0 / mfgp_set_tiny(h, 0) disables)
-    hipStream_t side;           // its high-priority side stream + fork / join events (created with the handle)
-    hipEvent_t ev_fork, ev_join;
-    int svgp_qs_packed;         // mfgp_set_svgp_qs_packed: mfgp_svgp_elbo_grad's q_sqrt / gq_sqrt as packed triangles
-    int step_fusion;            // mfgp_set_step_fusion: mfgp_gpr_adam_steps defers each step's reduction into the next flow launch
-    int resident;               // mfgp_set_resident: fp64 value+grad flow calls may skip the set-up launch
-    struct {                    // the last fp64 LML call on this handle, when it left its workspace set
-        const void* ws;         // up for the next one (k_grad's grad_next_setup); ws == nullptr: none
-        int n, p, d, flow_wgs;
-    } res;
-};
 
 namespace mfgp {
 
@@ -67,40 +39,6 @@ __attribute__((constructor)) static void segv_trace_install() {
     if (e && atoi(e) != 0) signal(SIGSEGV, segv_trace);
 }
 
-static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
-
-constexpr double GRAPH_JITTER = 1e-6;   // graph.py:96: K_full += 1e-6 I
-
-struct Carve {
-    char* base;
-    size_t off = 0;
-    explicit Carve(void* b) : base((char*)b) {}
-    template <class T>
-    T* take(size_t count) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += count * sizeof(T);
-        return p;
-    }
-};
-
-struct GprLayout {
-    int nb, npad, T, ppad, Tp, G, gstride, ng;
-    double *A, *R, *Xo, *Dd, *ldiag, *alpha, *zpart, *gpart, *items;
-    int* gorder;   // k_grad workgroup -> task table (+ key), built or verified by k_gram each call
-    int* cnt;   // reduce-arrival counter, zeroed by k_gram each call
-    int ncnt;
-    // k_chol_flow (flow_wgs > 0): flags (zeroed) + owner table (built or verified) by k_gram each call
-    int flow_wgs, nflags;
-    int *flags, *own;
-    double* pub;        // publication area (sentinel-filled by k_gram)
-    long npub;
-    long long* trace;   // k_chol_flow timeline (diagnostic; written only when enabled)
-    int ntrace;
-    int gchunk;         // k_grad's task chunk (m-tiles per task)
-    size_t bytes;
-};
-
 // The persistent Cholesky needs every workgroup resident (one per CU) and the owner table
 // to hold every tile; otherwise the launch-per-step sequence runs.
 static int flow_grid(int nb, int T, int Tp, int flow_wgs, int min_t) {
@@ -109,8 +47,7 @@ static int flow_grid(int nb, int T, int Tp, int flow_wgs, int min_t) {
     return flow_wgs;
 }
 
-static GprLayout gpr_layout(int nb, int n, int p, int d, void* ws, int grad_chunk, int nlf = 0, int flow_wgs = 0,
-                            int flow_min_t = 0) {
+GprLayout gpr_layout(int nb, int n, int p, int d, void* ws, int grad_chunk, int nlf, int flow_wgs, int flow_min_t) {
     GprLayout L;
     L.nb = nb;
     L.T = ceil_div(n, nb);
@@ -146,8 +83,6 @@ static GprLayout gpr_layout(int nb, int n, int p, int d, void* ws, int grad_chun
     L.bytes = c.off + 256;
     return L;
 }
-
-static inline hipError_t last() { return hipGetLastError(); }
 
 // Below this many 32-tiles the launch-per-step Cholesky is faster than the persistent flow (one
 // 256-workgroup launch costs more than a few short step launches): fp64 value+grad evaluation,
@@ -307,6 +242,10 @@ static void gram_lml_and_factor(hipStream_t s, const GprLayout& L, int n, int p,
     c.Dd = L.Dd; c.sD = 0; c.ldiag = L.ldiag; c.sL = 0; c.info = info;
     c.T = L.T; c.Tp = L.Tp; c.k = 0;
     launch_chol_steps<NB>(c, 1, s);
+}
+void gpr_factor(int nb, hipStream_t s, const GprLayout& L, int n, int p, int d, const double* X, int ldx,
+                const double* Y, int ldy, const double* theta, int* info, int nlf) {
+    TILE_CALL(nb, gram_lml_and_factor, s, L, n, p, d, X, ldx, Y, ldy, theta, info, nlf);
 }
 
 // Optional per-phase event marks (diagnostic timing; never used on the hot path).
@@ -636,6 +575,11 @@ __global__ void k_copy_block(const double* src, long lds, double* dst, long ldd,
         dst[(long)r * ldd + c] = src[(long)r * lds + c];
     }
 }
+void copy_block(hipStream_t s, const double* src, long lds, double* dst, long ldd, int rows, int cols) {
+    const long tot = (long)rows * cols;
+    hipLaunchKernelGGL(k_copy_block, dim3((int)std::min<long>((tot + 255) / 256, 2048)), dim3(256), 0, s, src, lds, dst,
+                       ldd, rows, cols);
+}
 
 template <int NB>
 static int predict_impl(mfgp_handle_t h, int n, int p, int d, int nstar, const double* X, int ldx, const double* Y,
@@ -665,29 +609,7 @@ static int predict_impl(mfgp_handle_t h, int n, int p, int d, int nstar, const d
     PredAArgs pa{L.Xo, ldr, P.Kmn, (long)P.nspad, P.Am, (long)P.nspad, P.Ts};
     PredOutArgs po{P.Am, (long)P.nspad, L.Xo, ldr, P.kdiag, mean, (long)ldm, var, L.T, L.Tp, nstar, p};
     launch_pred<NB>(pa, po, L.T, s);
-    if (cov) {
-        // base_conditional(full_cov=True): Kss - A^T A with A = L^{-1} Kmn (padded rows of A are 0)
-        if (nlf) (void)hipMemsetAsync(P.Kss, 0, sizeof(double) * (size_t)P.nspad * P.nspad, s);
-        GramArgs gs{};
-        gs.X1 = Xs; gs.ldx1 = ldxs; gs.n1 = nstar;
-        gs.X2 = Xs; gs.ldx2 = ldxs; gs.n2 = nstar;
-        gs.theta = theta; gs.D = d; gs.rbf_only = 0;
-        gs.out = P.Kss; gs.ldo = P.nspad; gs.padded = 0; gs.tiles_c = P.Ts; gs.nlf = nlf;
-        gs.diag_add = nlf ? GRAPH_JITTER : 0.0;   // graph.py:96 adds the jitter inside K(X*, X*) too
-        if (nlf) launch_gram<NB>(gs, P.Ts * P.Ts, 1, s);
-        else launch_gram_dense(gs, 1, P.nspad, P.nspad, s);
-        BgemmArgs b{};
-        b.A = P.Am; b.lda = P.nspad;
-        b.B = P.Am; b.ldb = P.nspad;
-        b.Cin = P.Kss; b.ldc = P.nspad; b.beta = 1.0;
-        b.D = P.Cov; b.ldd = P.nspad;
-        b.alpha = -1.0;
-        b.Mt = P.Ts; b.Nt = P.Ts; b.Kt = L.T;
-        launch_bgemm(NB, s, 1, 0, b, 1);
-        const long tot = (long)nstar * nstar;
-        hipLaunchKernelGGL(k_copy_block, dim3((int)std::min<long>((tot + 255) / 256, 2048)), dim3(256), 0, s, P.Cov,
-                           (long)P.nspad, cov, (long)ldc, nstar, nstar);
-    }
+    if (cov) cov_from_a<NB>(s, Xs, ldxs, nstar, theta, d, nlf, P.Am, P.nspad, L.T, P.Kss, P.Cov, cov, ldc);
     return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
 }
 
@@ -811,386 +733,9 @@ static int f32_predict(mfgp_handle_t h, int n, int p, int d, int ns, const float
     return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
 }
 
-// ---------------------------------------------------------------- cached posterior (mfgp_posterior.hip)
-// GPR cache (self-contained, laid out for the tile size it was built with):
-//   [X: n x (d + 1), dense][theta: G][LZ: Npad x (Npad + Ppad) = the factor's Xo rows, L^{-1} lower tiles | Z = L^{-1} Y]
-struct GprCache {
-    int npad, T, ppad, Tp, G;
-    long ldr;
-    double *X, *theta, *LZ;
-    size_t bytes;
-};
-static GprCache gpr_cache_layout(int nb, int nlf, int n, int p, int d, void* base) {
-    GprCache c;
-    c.T = ceil_div(n, nb);
-    c.npad = c.T * nb;
-    c.Tp = ceil_div(p, nb);
-    c.ppad = c.Tp * nb;
-    c.G = kernel_theta_size(nlf, d);
-    c.ldr = (long)c.npad + c.ppad;
-    Carve cv(base);
-    c.X = cv.take<double>((size_t)n * (d + 1));
-    c.theta = cv.take<double>((size_t)c.G);
-    c.LZ = cv.take<double>((size_t)c.npad * c.ldr);
-    c.bytes = cv.off + 256;
-    return c;
-}
-
-// m-tiles per k_post_a task.  A batch that fills the device with whole rows keeps them whole (no
-// partials to re-read); otherwise rows are cut so that the longest task is 8 tile products (a row
-// of up to 64 tiles then has at most 8 partials: one batch of loads in k_post_out).
-constexpr int POST_CHUNK = 8;
-static int post_chunk(int T, int Ts, int batch) { return (long)batch * T * Ts >= 256 ? T : POST_CHUNK; }
-
-struct PostLayout {
-    int Ts, nspad, chunk, ntask, ngrp;
-    double *Apart, *Bpart, *mpart, *vpart, *Am, *Kss, *Cov;   // GPR; Kss / Cov are null with cov = false
-                                                              // (design: launch_post full = 0 never touches them)
-    double *pa, *pb, *pm, *gm, *gv;                           // SVGP
-    int* cnt;
-    size_t bytes;
-};
-// svgp: batch = latents, T = Tm; gpr: batch = 1
-static PostLayout post_layout(int nb, int T, int Tp, int nstar, int batch, bool svgp, void* ws, bool cov = true) {
-    PostLayout P{};
-    P.Ts = ceil_div(nstar > 0 ? nstar : 1, nb);
-    P.nspad = P.Ts * nb;
-    P.chunk = post_chunk(T, P.Ts, batch);
-    P.ntask = post_ntasks(T, P.chunk, svgp ? 1 : 0);
-    P.ngrp = ceil_div(T, post_rg(nb));
-    Carve c(ws);
-    const size_t part = (size_t)batch * P.ntask * P.Ts * nb * nb;
-    P.Apart = c.take<double>(part);
-    P.cnt = c.take<int>((size_t)P.Ts);
-    if (svgp) {
-        P.Bpart = c.take<double>(part);
-        const size_t pp = (size_t)batch * P.ngrp * P.nspad;
-        P.pa = c.take<double>(pp);
-        P.pb = c.take<double>(pp);
-        P.pm = c.take<double>(pp);
-        P.gm = c.take<double>((size_t)batch * P.nspad);
-        P.gv = c.take<double>((size_t)batch * P.nspad);
-    } else {
-        P.mpart = c.take<double>((size_t)P.ngrp * P.nspad * Tp * nb);
-        P.vpart = c.take<double>((size_t)P.ngrp * P.nspad);
-        P.Am = c.take<double>((size_t)T * nb * P.nspad);
-        if (cov) {   // (the design calls keep A but never form a covariance block)
-            P.Kss = c.take<double>((size_t)P.nspad * P.nspad);
-            P.Cov = c.take<double>((size_t)P.nspad * P.nspad);
-        }
-    }
-    P.bytes = c.off + 256;
-    return P;
-}
-
-// The VJP calls' workspace: the predict layout, then the input-gradient partials, k_post_grad's
-// counters and (SVGP) the kept A / B of every latent.
-struct PostGradIO {
-    const double* gmean; long ldgm;
-    const double* gvar;
-    double* gX; long ldgx;
-};
-struct PostGradLayout {
-    double *gpart, *glat, *Am, *Bm;
-    int* gcnt;
-    size_t bytes;
-};
-static PostGradLayout post_grad_layout(int nb, const PostLayout& P, int T, int d, int batch, bool svgp, void* ws) {
-    PostGradLayout G{};
-    const size_t o = (P.bytes + 255) & ~(size_t)255;
-    Carve c(ws ? (char*)ws + o : nullptr);
-    G.gpart = c.take<double>((size_t)batch * P.ntask * P.Ts * nb * (d > 0 ? d : 1));
-    G.gcnt = c.take<int>((size_t)P.Ts * (1 + batch));
-    if (svgp) {
-        G.glat = c.take<double>((size_t)batch * P.Ts * nb * (d > 0 ? d : 1));
-        G.Am = c.take<double>((size_t)batch * T * nb * P.nspad);
-        G.Bm = c.take<double>((size_t)batch * T * nb * P.nspad);
-    }
-    G.bytes = o + c.off + 256;
-    return G;
-}
-
-template <int NB>
-static int gpr_posterior_build_impl(mfgp_handle_t h, int nlf, int n, int p, int d, const double* X, int ldx,
-                                    const double* Y, int ldy, const double* theta, void* ws, size_t ws_bytes,
-                                    void* cache, size_t cache_bytes, int* info) {
-    const GprLayout L = gpr_layout(NB, n, p, d, ws, h->grad_chunk, nlf);
-    const GprCache c = gpr_cache_layout(NB, nlf, n, p, d, cache);
-    if (ws_bytes < L.bytes || cache_bytes < c.bytes) return MFGP_ERR_WORKSPACE;
-    hipStream_t s = h->stream;
-    gram_lml_and_factor<NB>(s, L, n, p, d, X, ldx, Y, ldy, theta, info, nlf);
-    auto copy = [&](const double* src, long lds, double* dst, long ldd, int rows, int cols) {
-        const long tot = (long)rows * cols;
-        hipLaunchKernelGGL(k_copy_block, dim3((int)std::min<long>((tot + 255) / 256, 2048)), dim3(256), 0, s, src, lds,
-                           dst, ldd, rows, cols);
-    };
-    copy(X, ldx, c.X, d + 1, n, d + 1);
-    copy(theta, c.G, c.theta, c.G, 1, c.G);
-    copy(L.Xo, c.ldr, c.LZ, c.ldr, c.npad, (int)c.ldr);
-    return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
-}
-
-template <int NB>
-static int gpr_posterior_predict_impl(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar, const void* cache,
-                                      size_t cache_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes,
-                                      double* mean, int ldm, double* var, double* cov, int ldc,
-                                      const PostGradIO* g = nullptr) {
-    const GprCache c = gpr_cache_layout(NB, nlf, n, p, d, const_cast<void*>(cache));
-    const PostLayout P = post_layout(NB, c.T, c.Tp, nstar, 1, false, ws);
-    const PostGradLayout G = post_grad_layout(NB, P, c.T, d, 1, false, ws);
-    if (cache_bytes < c.bytes || ws_bytes < (g ? G.bytes : P.bytes)) return MFGP_ERR_WORKSPACE;
-    hipStream_t s = h->stream;
-    PostArgs a{};
-    a.Li = c.LZ; a.ldl = c.ldr; a.sL = 0;
-    a.X1 = c.X; a.ldx1 = d + 1; a.n1 = n;
-    a.theta = c.theta; a.stheta = 0;
-    a.Xs = Xs; a.ldxs = ldxs; a.nstar = nstar;
-    a.D = d; a.nlf = nlf;
-    a.T = c.T; a.Ts = P.Ts; a.chunk = P.chunk; a.full = 0; a.ntask = P.ntask; a.ngrp = P.ngrp;
-    a.Apart = P.Apart; a.cnt = P.cnt;
-    a.Zc = c.LZ + c.npad; a.ldz = c.ldr; a.Tp = c.Tp; a.p = p;
-    a.Am = (cov || g) ? P.Am : nullptr; a.ldam = P.nspad;
-    a.mpart = P.mpart; a.vpart = P.vpart;
-    a.mean = mean; a.ldm = ldm; a.var = var;
-    if (g) {
-        a.gmean = g->gmean; a.ldgm = g->ldgm; a.gvar = g->gvar;
-        a.gpart = G.gpart; a.glat = G.glat; a.gcnt = G.gcnt;
-        a.gX = g->gX; a.ldgx = g->ldgx;
-    }
-    launch_post<NB>(a, 1, s);
-    if (g) launch_post_grad<NB>(a, 1, s);
-    if (cov) {
-        // base_conditional(full_cov=True): Kss - A^T A, as the tail of predict_impl (theta from the cache)
-        if (nlf) (void)hipMemsetAsync(P.Kss, 0, sizeof(double) * (size_t)P.nspad * P.nspad, s);
-        GramArgs gs{};
-        gs.X1 = Xs; gs.ldx1 = ldxs; gs.n1 = nstar;
-        gs.X2 = Xs; gs.ldx2 = ldxs; gs.n2 = nstar;
-        gs.theta = c.theta; gs.D = d; gs.rbf_only = 0;
-        gs.out = P.Kss; gs.ldo = P.nspad; gs.padded = 0; gs.tiles_c = P.Ts; gs.nlf = nlf;
-        gs.diag_add = nlf ? GRAPH_JITTER : 0.0;
-        if (nlf) launch_gram<NB>(gs, P.Ts * P.Ts, 1, s);
-        else launch_gram_dense(gs, 1, P.nspad, P.nspad, s);
-        BgemmArgs b{};
-        b.A = P.Am; b.lda = P.nspad;
-        b.B = P.Am; b.ldb = P.nspad;
-        b.Cin = P.Kss; b.ldc = P.nspad; b.beta = 1.0;
-        b.D = P.Cov; b.ldd = P.nspad;
-        b.alpha = -1.0;
-        b.Mt = P.Ts; b.Nt = P.Ts; b.Kt = c.T;
-        launch_bgemm(NB, s, 1, 0, b, 1);
-        const long tot = (long)nstar * nstar;
-        hipLaunchKernelGGL(k_copy_block, dim3((int)std::min<long>((tot + 255) / 256, 2048)), dim3(256), 0, s, P.Cov,
-                           (long)P.nspad, cov, (long)ldc, nstar, nstar);
-    }
-    return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
-}
-
-// Leave-group-out workspace: the task table, the arrival counters and the chunk partials.
-// Tasks: first fit in order closes a task only when the next group does not fit, so every task but
-// the last holds at least 33 - gmax columns, and two consecutive tasks together more than 32.
-// Chunks: 4 steps of 32 rows (a task at Goku's 37 steps is spread over 10 workgroups), longer
-// beyond 128 steps so that the last workgroup sums at most 32 partials.
-struct LoLayout {
-    int chunk, nch, ny, ntmax;
-    int *tab, *cnt;
-    double* part;
-    size_t bytes;
-};
-static LoLayout lo_layout(int n, int p, int ngroups, int nrows, int gmax, void* ws) {
-    LoLayout L{};
-    const int T32 = ceil_div(n, 32);
-    L.chunk = T32 > 128 ? ceil_div(T32, 32) : 4;
-    L.nch = ceil_div(T32, L.chunk);
-    L.ny = ceil_div(p, 32 * LO_PT);
-    L.ntmax = std::min(ngroups, std::min((nrows - 1) / (LO_W + 1 - gmax) + 1, 2 * (nrows / (LO_W + 1)) + 1));
-    Carve c(ws);
-    L.tab = c.take<int>((size_t)L.ntmax + 2);
-    L.cnt = c.take<int>((size_t)L.ntmax * L.ny);
-    L.part = c.take<double>((size_t)L.ntmax * L.nch * L.ny * 32 * 32 * (1 + LO_PT));
-    L.bytes = c.off + 256;
-    return L;
-}
-
-// Design workspace: the counters first (one memset per call zeroes exactly that block), then the
-// predict layout of the nref + ncand stacked points without its covariance blocks (A is kept there),
-// then the forward's outputs (the mean is formed and not used: the forward is the predict call's own)
-// and the two kernels' partials.
-struct DesignLayout {
-    PostLayout P;
-    int nall, Tr, Tc, nrun, ncb, nrch;
-    int* cnt;            // [Tc] k_design_score, then [ncb] k_design_row
-    size_t cnt_bytes;
-    double *mean, *var, *dpart, *rpart;
-    size_t bytes;
-};
-static DesignLayout design_layout(int nb, int T, int Tp, int p, int nref, int ncand, void* ws) {
-    DesignLayout L{};
-    L.nall = nref + ncand;
-    L.Tr = ceil_div(nref > 0 ? nref : 1, nb);
-    L.Tc = ceil_div(ncand > 0 ? ncand : 1, nb);
-    L.nrun = ceil_div(L.Tr, design_run(nb));
-    L.ncb = ceil_div(L.nall > 0 ? L.nall : 1, NTHREADS);
-    L.nrch = ceil_div(T * nb, DESIGN_RROWS);
-    Carve c(ws);
-    L.cnt_bytes = (sizeof(int) * ((size_t)L.Tc + L.ncb) + 15) & ~(size_t)15;
-    L.cnt = c.take<int>(L.cnt_bytes / sizeof(int));
-    const size_t o = (c.off + 255) & ~(size_t)255;
-    L.P = post_layout(nb, T, Tp, L.nall, 1, false, ws ? (char*)ws + o : nullptr, false);
-    const size_t pb = (L.P.bytes + 255) & ~(size_t)255;
-    Carve c2(ws ? (char*)ws + o + pb : nullptr);
-    L.mean = c2.take<double>((size_t)L.nall * p);
-    L.var = c2.take<double>((size_t)L.nall);
-    L.dpart = c2.take<double>((size_t)L.nrun * L.Tc * nb);
-    L.rpart = c2.take<double>((size_t)L.nrch * L.ncb * NTHREADS);
-    L.bytes = o + pb + c2.off + 256;
-    return L;
-}
-
-// mode 0: score (refresh: the forward first); mode 1: append row k of E for the picked candidate
-template <int NB>
-static int gpr_posterior_design_impl(mfgp_handle_t h, int nlf, int n, int p, int d, const void* cache,
-                                     size_t cache_bytes, const double* Xall, int ldx, int nref, int ncand,
-                                     const double* w, double* E, int ldE, int k, void* ws, size_t ws_bytes,
-                                     double* score, int refresh, const int* pick) {
-    const GprCache c = gpr_cache_layout(NB, nlf, n, p, d, const_cast<void*>(cache));
-    const DesignLayout L = design_layout(NB, c.T, c.Tp, p, nref, ncand, ws);
-    if (cache_bytes < c.bytes || ws_bytes < L.bytes) return MFGP_ERR_WORKSPACE;
-    hipStream_t s = h->stream;
-    if (!pick && refresh) {
-        PostArgs a{};
-        a.Li = c.LZ; a.ldl = c.ldr; a.sL = 0;
-        a.X1 = c.X; a.ldx1 = d + 1; a.n1 = n;
-        a.theta = c.theta; a.stheta = 0;
-        a.Xs = Xall; a.ldxs = ldx; a.nstar = L.nall;
-        a.D = d; a.nlf = nlf;
-        a.T = c.T; a.Ts = L.P.Ts; a.chunk = L.P.chunk; a.full = 0; a.ntask = L.P.ntask; a.ngrp = L.P.ngrp;
-        a.Apart = L.P.Apart; a.cnt = L.P.cnt;
-        a.Zc = c.LZ + c.npad; a.ldz = c.ldr; a.Tp = c.Tp; a.p = p;
-        a.Am = L.P.Am; a.ldam = L.P.nspad;
-        a.mpart = L.P.mpart; a.vpart = L.P.vpart;
-        a.mean = L.mean; a.ldm = p; a.var = L.var;
-        launch_post<NB>(a, 1, s);
-    }
-    (void)hipMemsetAsync(L.cnt, 0, L.cnt_bytes, s);
-    DesignArgs g{};
-    g.Am = L.P.Am; g.ldam = L.P.nspad; g.npad = c.npad;
-    g.var = L.var;
-    g.Xall = Xall; g.ldx = ldx; g.nref = nref; g.ncand = ncand;
-    g.theta = c.theta; g.noise = c.theta + c.G - 1;   // the likelihood variance closes both theta layouts
-    g.D = d; g.nlf = nlf;
-    g.w = w;
-    g.E = E; g.ldE = ldE; g.k = k;
-    g.T = c.T; g.Tr = L.Tr; g.Tc = L.Tc; g.nrun = L.nrun;
-    g.dpart = L.dpart; g.dcnt = L.cnt; g.score = score;
-    g.pick = pick; g.Erow = pick ? E + (size_t)k * ldE : nullptr;
-    g.ncb = L.ncb; g.nrch = L.nrch; g.rpart = L.rpart; g.rcnt = L.cnt + L.Tc;
-    if (pick) launch_design_row(g, s);
-    else launch_design_score<NB>(g, s);
-    return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
-}
-
-// SVGP cache: [Z: m x (d + 1)][thetas: l x G][W: p x l][q_mu^T: l x Mpad, zero padded]
-//             [Lm^{-1}: l x Mpad x Mpad][C = Lq^T Lm^{-1}: l x Mpad x Mpad]
-struct SvgpCache {
-    int Tm, mpad, G;
-    double *Z, *thetas, *W, *qmu, *Li, *C;
-    size_t bytes;
-};
-static SvgpCache svgp_cache_layout(int nb, int m, int l, int p, int d, void* base) {
-    SvgpCache c;
-    c.Tm = ceil_div(m, nb);
-    c.mpad = c.Tm * nb;
-    c.G = theta_size(d);
-    const size_t mm = (size_t)c.mpad * c.mpad;
-    Carve cv(base);
-    c.Z = cv.take<double>((size_t)m * (d + 1));
-    c.thetas = cv.take<double>((size_t)l * c.G);
-    c.W = cv.take<double>((size_t)p * l);
-    c.qmu = cv.take<double>((size_t)l * c.mpad);
-    c.Li = cv.take<double>(mm * l);
-    c.C = cv.take<double>(mm * l);
-    c.bytes = cv.off + 256;
-    return c;
-}
-
-// q_mu [m][L] -> [L][Mpad], zero padded
-__global__ void k_post_qmu_pad(const double* q_mu, int m, int L, int mpad, double* out) {
-    const long total = (long)L * mpad;
-    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-        const int l = (int)(e / mpad), r = (int)(e % mpad);
-        out[e] = r < m ? q_mu[(long)r * L + l] : 0.0;
-    }
-}
-
-static int svgp_posterior_build_impl(mfgp_handle_t h, int m, int l, int p, int d, const double* Z, int ldz,
-                                     const double* thetas, const double* q_mu, const double* q_sqrt, const double* W,
-                                     double jitter, void* ws, size_t ws_bytes, void* cache, size_t cache_bytes,
-                                     int* info) {
-    const SvgpCache c = svgp_cache_layout(h->nb, m, l, p, d, cache);
-    if (cache_bytes < c.bytes || ws_bytes < svgp_posterior_factor_bytes(h->nb, m, l)) return MFGP_ERR_WORKSPACE;
-    hipStream_t s = h->stream;
-    const int rc = svgp_posterior_factor(s, h->nb, m, l, d, Z, ldz, thetas, q_sqrt, jitter, ws, ws_bytes, c.Li, c.C,
-                                         info);
-    if (rc) return rc == -2 ? MFGP_ERR_WORKSPACE : MFGP_ERR_LAUNCH;
-    auto copy = [&](const double* src, long lds, double* dst, long ldd, int rows, int cols) {
-        const long tot = (long)rows * cols;
-        hipLaunchKernelGGL(k_copy_block, dim3((int)std::min<long>((tot + 255) / 256, 2048)), dim3(256), 0, s, src, lds,
-                           dst, ldd, rows, cols);
-    };
-    copy(Z, ldz, c.Z, d + 1, m, d + 1);
-    copy(thetas, c.G, c.thetas, c.G, l, c.G);
-    if (W) copy(W, l, c.W, l, p, l);
-    const long tot = (long)l * c.mpad;
-    hipLaunchKernelGGL(k_post_qmu_pad, dim3((int)std::min<long>((tot + 255) / 256, 2048)), dim3(256), 0, s, q_mu, m, l,
-                       c.mpad, c.qmu);
-    return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
-}
-
-static int svgp_posterior_predict_impl(mfgp_handle_t h, int nstar, int m, int l, int p, int d, int mixed,
-                                       const void* cache, size_t cache_bytes, const double* Xs, int ldxs, void* ws,
-                                       size_t ws_bytes, double* f_mu, double* f_var,
-                                       const PostGradIO* g = nullptr) {
-    const SvgpCache c = svgp_cache_layout(h->nb, m, l, p, d, const_cast<void*>(cache));
-    const PostLayout P = post_layout(h->nb, c.Tm, 0, nstar, l, true, ws);
-    const PostGradLayout G = post_grad_layout(h->nb, P, c.Tm, d, l, true, ws);
-    if (cache_bytes < c.bytes || ws_bytes < (g ? G.bytes : P.bytes)) return MFGP_ERR_WORKSPACE;
-    const long mm = (long)c.mpad * c.mpad;
-    PostArgs a{};
-    a.Li = c.Li; a.ldl = c.mpad; a.sL = mm;
-    a.C = c.C; a.ldc = c.mpad; a.sC = mm;
-    a.X1 = c.Z; a.ldx1 = d + 1; a.n1 = m;
-    a.theta = c.thetas; a.stheta = c.G;
-    a.Xs = Xs; a.ldxs = ldxs; a.nstar = nstar;
-    a.D = d; a.nlf = 0;
-    a.T = c.Tm; a.Ts = P.Ts; a.chunk = P.chunk; a.full = 1; a.ntask = P.ntask; a.ngrp = P.ngrp;
-    a.Apart = P.Apart; a.Bpart = P.Bpart; a.cnt = P.cnt;
-    a.p = p;
-    a.qmu = c.qmu; a.pa = P.pa; a.pb = P.pb; a.pm = P.pm; a.gm = P.gm; a.gv = P.gv;
-    a.W = mixed ? c.W : nullptr;
-    a.f_mu = f_mu; a.f_var = f_var;
-    if (g) {
-        a.Am = G.Am; a.Bm = G.Bm; a.ldam = P.nspad; a.sAm = (long)c.mpad * P.nspad;
-        a.gmean = g->gmean; a.ldgm = g->ldgm; a.gvar = g->gvar;
-        a.gpart = G.gpart; a.glat = G.glat; a.gcnt = G.gcnt;
-        a.gX = g->gX; a.ldgx = g->ldgx;
-    }
-    if (h->nb == 64) launch_post<64>(a, l, h->stream);
-    else launch_post<32>(a, l, h->stream);
-    if (g) {
-        if (h->nb == 64) launch_post_grad<64>(a, l, h->stream);
-        else launch_post_grad<32>(a, l, h->stream);
-    }
-    return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
-}
-
 }  // namespace mfgp
 
 using namespace mfgp;
-
-#define CHECK_H(h) \
-    if ((h) == nullptr) return MFGP_ERR_ARG
-#define CHECK_D(d) \
-    if ((d) < 1 || (d) > MFGP_MAX_D) return MFGP_ERR_DIM
 
 extern "C" {
 
@@ -1374,8 +919,7 @@ static int gram_common(mfgp_handle_t h, int n1, int n2, int d, const double* X1,
     const int nb = h->nb;
     g.tiles_c = ceil_div(n2, nb);
     const int blocks = ceil_div(n1, nb) * g.tiles_c;
-    if (nb == 64) launch_gram<64>(g, blocks, 1, h->stream);
-    else launch_gram<32>(g, blocks, 1, h->stream);
+    TILE_CALL(nb, launch_gram, g, blocks, 1, h->stream);
     return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
 }
 
@@ -1435,11 +979,8 @@ int mfgp_gmf_gpr_lml(mfgp_handle_t h, int nlf, int n, int p, int d, const double
     CHECK_D(d);
     CHECK_LF(nlf);
     if (n < 1 || p < 1 || !X || !Y || !theta || !ws || !out || !info) return MFGP_ERR_ARG;
-    if (h->nb == 64)
-        return gpr_value_grad<64>(h, n, p, d, X, ldx, Y, ldy, (double*)theta, want_grad, ws, ws_bytes, out, info,
-                                  nullptr, nullptr, nlf);
-    return gpr_value_grad<32>(h, n, p, d, X, ldx, Y, ldy, (double*)theta, want_grad, ws, ws_bytes, out, info,
-                              nullptr, nullptr, nlf);
+    return TILE_CALL(h->nb, gpr_value_grad, h, n, p, d, X, ldx, Y, ldy, (double*)theta, want_grad, ws, ws_bytes, out,
+                     info, nullptr, nullptr, nlf);
 }
 
 int mfgp_gmf_gpr_predict_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar, size_t* bytes) {
@@ -1460,11 +1001,8 @@ int mfgp_gmf_gpr_predict(mfgp_handle_t h, int nlf, int n, int p, int d, int nsta
     if (n < 1 || p < 1 || nstar < 0 || !X || !Y || !theta || !ws || !info) return MFGP_ERR_ARG;
     if (nstar == 0) return MFGP_OK;
     if (!Xs || !mean || !var) return MFGP_ERR_ARG;
-    if (h->nb == 64)
-        return predict_impl<64>(h, n, p, d, nstar, X, ldx, Y, ldy, Xs, ldxs, theta, ws, ws_bytes, mean, ldm, var,
-                                info, nlf);
-    return predict_impl<32>(h, n, p, d, nstar, X, ldx, Y, ldy, Xs, ldxs, theta, ws, ws_bytes, mean, ldm, var, info,
-                            nlf);
+    return TILE_CALL(h->nb, predict_impl, h, n, p, d, nstar, X, ldx, Y, ldy, Xs, ldxs, theta, ws, ws_bytes, mean, ldm,
+                     var, info, nlf);
 }
 
 int mfgp_gpr_workspace_size(mfgp_handle_t h, int n, int p, int d, size_t* bytes) {
@@ -1480,11 +1018,8 @@ int mfgp_gpr_lml(mfgp_handle_t h, int n, int p, int d, const double* X, int ldx,
     CHECK_H(h);
     CHECK_D(d);
     if (n < 1 || p < 1 || !X || !Y || !theta || !ws || !out || !info) return MFGP_ERR_ARG;
-    if (h->nb == 64)
-        return gpr_value_grad<64>(h, n, p, d, X, ldx, Y, ldy, (double*)theta, want_grad, ws, ws_bytes, out, info,
-                                  nullptr);
-    return gpr_value_grad<32>(h, n, p, d, X, ldx, Y, ldy, (double*)theta, want_grad, ws, ws_bytes, out, info,
-                              nullptr);
+    return TILE_CALL(h->nb, gpr_value_grad, h, n, p, d, X, ldx, Y, ldy, (double*)theta, want_grad, ws, ws_bytes, out,
+                     info, nullptr);
 }
 
 int mfgp_gpr_adam_step(mfgp_handle_t h, int n, int p, int d, const double* X, int ldx, const double* Y, int ldy,
@@ -1500,8 +1035,7 @@ int mfgp_gpr_adam_step(mfgp_handle_t h, int n, int p, int d, const double* X, in
     f.theta = theta; f.u = u; f.m = m; f.v = v; f.trainable = trainable; f.tie = tie; f.step = step;
     f.lr = lr; f.b1 = beta1; f.b2 = beta2; f.eps = eps; f.loss_hist = loss_hist;
     f.noise_index = theta_size(d) - 1;
-    if (h->nb == 64) return gpr_value_grad<64>(h, n, p, d, X, ldx, Y, ldy, theta, 1, ws, ws_bytes, out, info, &f);
-    return gpr_value_grad<32>(h, n, p, d, X, ldx, Y, ldy, theta, 1, ws, ws_bytes, out, info, &f);
+    return TILE_CALL(h->nb, gpr_value_grad, h, n, p, d, X, ldx, Y, ldy, theta, 1, ws, ws_bytes, out, info, &f);
 }
 
 int mfgp_gpr_adam_steps(mfgp_handle_t h, int n, int p, int d, const double* X, int ldx, const double* Y, int ldy,
@@ -1537,11 +1071,8 @@ int mfgp_gpr_lml_phase_times(mfgp_handle_t h, int n, int p, int d, const double*
     if (n < 1 || p < 1 || !X || !Y || !theta || !ws || !out || !info || !ms) return MFGP_ERR_ARG;
     PhaseMarks pm;
     for (int i = 0; i < 6; ++i) (void)hipEventCreate(&pm.ev[i]);
-    int rc = (h->nb == 64)
-                 ? gpr_value_grad<64>(h, n, p, d, X, ldx, Y, ldy, (double*)theta, 1, ws, ws_bytes, out, info,
-                                      nullptr, &pm)
-                 : gpr_value_grad<32>(h, n, p, d, X, ldx, Y, ldy, (double*)theta, 1, ws, ws_bytes, out, info,
-                                      nullptr, &pm);
+    int rc = TILE_CALL(h->nb, gpr_value_grad, h, n, p, d, X, ldx, Y, ldy, (double*)theta, 1, ws, ws_bytes, out, info,
+                       nullptr, &pm);
     if (rc == MFGP_OK) {
         (void)hipEventSynchronize(pm.ev[pm.count - 1]);
         for (int i = 0; i + 1 < pm.count; ++i) (void)hipEventElapsedTime(&ms[i], pm.ev[i], pm.ev[i + 1]);
@@ -1573,10 +1104,8 @@ int mfgp_gpr_predict(mfgp_handle_t h, int n, int p, int d, int nstar, const doub
     if (n < 1 || p < 1 || nstar < 0 || !X || !Y || !theta || !ws || !info) return MFGP_ERR_ARG;
     if (nstar == 0) return MFGP_OK;
     if (!Xs || !mean || !var) return MFGP_ERR_ARG;
-    if (h->nb == 64)
-        return predict_impl<64>(h, n, p, d, nstar, X, ldx, Y, ldy, Xs, ldxs, theta, ws, ws_bytes, mean, ldm, var,
-                                info);
-    return predict_impl<32>(h, n, p, d, nstar, X, ldx, Y, ldy, Xs, ldxs, theta, ws, ws_bytes, mean, ldm, var, info);
+    return TILE_CALL(h->nb, predict_impl, h, n, p, d, nstar, X, ldx, Y, ldy, Xs, ldxs, theta, ws, ws_bytes, mean, ldm,
+                     var, info);
 }
 
 int mfgp_gpr_predict_cov_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar, size_t* bytes) {
@@ -1596,11 +1125,8 @@ int mfgp_gpr_predict_cov(mfgp_handle_t h, int nlf, int n, int p, int d, int nsta
     if (n < 1 || p < 1 || nstar < 0 || !X || !Y || !theta || !ws || !info) return MFGP_ERR_ARG;
     if (nstar == 0) return MFGP_OK;
     if (!Xs || !mean || !var || !cov || ldc < nstar) return MFGP_ERR_ARG;
-    if (h->nb == 64)
-        return predict_impl<64>(h, n, p, d, nstar, X, ldx, Y, ldy, Xs, ldxs, theta, ws, ws_bytes, mean, ldm, var,
-                                info, nlf, cov, ldc);
-    return predict_impl<32>(h, n, p, d, nstar, X, ldx, Y, ldy, Xs, ldxs, theta, ws, ws_bytes, mean, ldm, var, info,
-                            nlf, cov, ldc);
+    return TILE_CALL(h->nb, predict_impl, h, n, p, d, nstar, X, ldx, Y, ldy, Xs, ldxs, theta, ws, ws_bytes, mean, ldm,
+                     var, info, nlf, cov, ldc);
 }
 
 int mfgp_potrf_inv_workspace_size(mfgp_handle_t h, int n, int batch, size_t* bytes) {
@@ -1614,8 +1140,7 @@ int mfgp_potrf_inv(mfgp_handle_t h, int n, int batch, const double* A, int lda, 
                    double* Linv, int ldl, long sL, double* ldiag, int* info) {
     CHECK_H(h);
     if (n < 1 || batch < 1 || !A || !ws || !Linv || !info) return MFGP_ERR_ARG;
-    if (h->nb == 64) return potrf_inv_impl<64>(h, n, batch, A, lda, sA, ws, ws_bytes, Linv, ldl, sL, ldiag, info);
-    return potrf_inv_impl<32>(h, n, batch, A, lda, sA, ws, ws_bytes, Linv, ldl, sL, ldiag, info);
+    return TILE_CALL(h->nb, potrf_inv_impl, h, n, batch, A, lda, sA, ws, ws_bytes, Linv, ldl, sL, ldiag, info);
 }
 
 int mfgp_svgp_workspace_size(mfgp_handle_t h, int n, int m, int l, int p, int d, size_t* bytes) {
@@ -1820,244 +1345,6 @@ int mfgp_svgp_predict_cov(mfgp_handle_t h, int mode, int nstar, int m, int l, in
     const int rc = svgp_predict_cov_impl(h->stream, h->nb, mode, nstar, m, l, p, d, Xs, ldxs, Z, ldz, thetas, q_mu,
                                          q_sqrt, W, jitter, ws, ws_bytes, g_mu, g_var, f_mu, f_var, f_cov, info);
     return rc == -2 ? MFGP_ERR_WORKSPACE : (rc ? MFGP_ERR_LAUNCH : MFGP_OK);
-}
-
-// ---------------------------------------------------------------- cached posterior
-int mfgp_gpr_posterior_size(mfgp_handle_t h, int nlf, int n, int p, int d, size_t* bytes) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (nlf < 0 || nlf > MFGP_MAX_LF || n < 1 || p < 1 || !bytes) return MFGP_ERR_ARG;
-    *bytes = gpr_cache_layout(h->nb, nlf, n, p, d, nullptr).bytes;
-    return MFGP_OK;
-}
-
-int mfgp_gpr_posterior_build(mfgp_handle_t h, int nlf, int n, int p, int d, const double* X, int ldx, const double* Y,
-                             int ldy, const double* theta, void* ws, size_t ws_bytes, void* cache, size_t cache_bytes,
-                             int* info) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (nlf < 0 || nlf > MFGP_MAX_LF) return MFGP_ERR_ARG;
-    if (n < 1 || p < 1 || !X || !Y || !theta || !ws || !cache || !info || ldx < d + 1 || ldy < p) return MFGP_ERR_ARG;
-    if (h->nb == 64)
-        return gpr_posterior_build_impl<64>(h, nlf, n, p, d, X, ldx, Y, ldy, theta, ws, ws_bytes, cache, cache_bytes,
-                                            info);
-    return gpr_posterior_build_impl<32>(h, nlf, n, p, d, X, ldx, Y, ldy, theta, ws, ws_bytes, cache, cache_bytes, info);
-}
-
-int mfgp_gpr_posterior_predict_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar,
-                                              size_t* bytes) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (nlf < 0 || nlf > MFGP_MAX_LF || n < 1 || p < 1 || nstar < 1 || !bytes) return MFGP_ERR_ARG;
-    const GprCache c = gpr_cache_layout(h->nb, nlf, n, p, d, nullptr);
-    *bytes = post_layout(h->nb, c.T, c.Tp, nstar, 1, false, nullptr).bytes;
-    return MFGP_OK;
-}
-
-int mfgp_gpr_posterior_predict(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar, const void* cache,
-                               size_t cache_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes, double* mean,
-                               int ldm, double* var, double* cov, int ldc) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (nlf < 0 || nlf > MFGP_MAX_LF) return MFGP_ERR_ARG;
-    if (n < 1 || p < 1 || nstar < 1 || !cache || !Xs || !ws || !mean || !var || ldxs < d + 1 || ldm < p)
-        return MFGP_ERR_ARG;
-    if (cov && ldc < nstar) return MFGP_ERR_ARG;
-    if (h->nb == 64)
-        return gpr_posterior_predict_impl<64>(h, nlf, n, p, d, nstar, cache, cache_bytes, Xs, ldxs, ws, ws_bytes, mean,
-                                              ldm, var, cov, ldc);
-    return gpr_posterior_predict_impl<32>(h, nlf, n, p, d, nstar, cache, cache_bytes, Xs, ldxs, ws, ws_bytes, mean,
-                                          ldm, var, cov, ldc);
-}
-
-int mfgp_gpr_posterior_predict_vjp_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar,
-                                                  size_t* bytes) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (nlf != 0 || n < 1 || p < 1 || nstar < 1 || !bytes) return MFGP_ERR_ARG;
-    const GprCache c = gpr_cache_layout(h->nb, nlf, n, p, d, nullptr);
-    const PostLayout P = post_layout(h->nb, c.T, c.Tp, nstar, 1, false, nullptr);
-    *bytes = post_grad_layout(h->nb, P, c.T, d, 1, false, nullptr).bytes;
-    return MFGP_OK;
-}
-
-int mfgp_gpr_posterior_predict_vjp(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar, const void* cache,
-                                   size_t cache_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes,
-                                   double* mean, int ldm, double* var, const double* gmean, int ldgm,
-                                   const double* gvar, double* gX, int ldgx) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (nlf != 0) return MFGP_ERR_ARG;   // the graph kernel's per-source derivative is not built
-    if (nstar == 0) return MFGP_OK;
-    if (n < 1 || p < 1 || nstar < 0 || !cache || !Xs || !ws || !mean || !var || !gX || ldxs < d + 1 || ldm < p ||
-        ldgx < d + 1)
-        return MFGP_ERR_ARG;
-    if (gmean && ldgm < p) return MFGP_ERR_ARG;
-    const PostGradIO g{gmean, ldgm, gvar, gX, ldgx};
-    if (h->nb == 64)
-        return gpr_posterior_predict_impl<64>(h, nlf, n, p, d, nstar, cache, cache_bytes, Xs, ldxs, ws, ws_bytes, mean,
-                                              ldm, var, nullptr, 0, &g);
-    return gpr_posterior_predict_impl<32>(h, nlf, n, p, d, nstar, cache, cache_bytes, Xs, ldxs, ws, ws_bytes, mean,
-                                          ldm, var, nullptr, 0, &g);
-}
-
-int mfgp_gpr_posterior_leave_out_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int ngroups, int nrows,
-                                                size_t* bytes) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (nlf < 0 || nlf > MFGP_MAX_LF || n < 1 || p < 1 || ngroups < 1 || nrows < ngroups || !bytes)
-        return MFGP_ERR_ARG;
-    *bytes = lo_layout(n, p, ngroups, nrows, LO_W, nullptr).bytes;   // groups of any size up to 32
-    return MFGP_OK;
-}
-
-int mfgp_gpr_posterior_leave_out(mfgp_handle_t h, int nlf, int n, int p, int d, const void* cache, size_t cache_bytes,
-                                 int ngroups, const int* offsets, const int* rows, int nrows, int gmax, void* ws,
-                                 size_t ws_bytes, double* resid, int ldr, double* cov, int ldc, double* logdens,
-                                 int* info) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (nlf < 0 || nlf > MFGP_MAX_LF || ngroups < 0 || gmax < 1 || gmax > LO_W) return MFGP_ERR_ARG;
-    if (ngroups == 0) return MFGP_OK;
-    if (n < 1 || p < 1 || nrows < ngroups || !cache || !offsets || !rows || !ws || !resid || !logdens || !info ||
-        ldr < p || (cov && ldc < gmax))
-        return MFGP_ERR_ARG;
-    const GprCache c = gpr_cache_layout(h->nb, nlf, n, p, d, const_cast<void*>(cache));
-    const LoLayout L = lo_layout(n, p, ngroups, nrows, gmax, ws);
-    if (cache_bytes < c.bytes || ws_bytes < L.bytes) return MFGP_ERR_WORKSPACE;
-    LoArgs a{};
-    a.LZ = c.LZ; a.ldr = c.ldr; a.npad = c.npad;
-    a.noise = c.theta + c.G - 1;   // the likelihood variance closes both theta layouts
-    a.n = n; a.p = p;
-    a.ngroups = ngroups; a.nrows = nrows; a.gmax = gmax;
-    a.offsets = offsets; a.rows = rows;
-    a.ntmax = L.ntmax; a.chunk = L.chunk; a.nch = L.nch; a.ny = L.ny;
-    a.tab = L.tab; a.cnt = L.cnt; a.part = L.part;
-    a.resid = resid; a.ldres = ldr; a.cov = cov; a.ldc = ldc; a.logdens = logdens; a.info = info;
-    launch_leave_out(a, h->stream);
-    return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
-}
-
-static bool design_geometry_ok(int nlf, int n, int p, int nref, int ncand) {
-    return nlf >= 0 && nlf <= MFGP_MAX_LF && n >= 1 && p >= 1 && nref >= 0 && ncand >= 0 &&
-           (long)nref + ncand <= 0x7fffffffL - 4096;
-}
-
-int mfgp_gpr_posterior_design_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int nref, int ncand,
-                                             int qmax, size_t* bytes) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (!design_geometry_ok(nlf, n, p, nref, ncand) || qmax < 0 || qmax > DESIGN_MAXQ || !bytes) return MFGP_ERR_ARG;
-    const GprCache c = gpr_cache_layout(h->nb, nlf, n, p, d, nullptr);
-    *bytes = design_layout(h->nb, c.T, c.Tp, p, nref, ncand, nullptr).bytes;
-    return MFGP_OK;
-}
-
-int mfgp_gpr_posterior_design_score(mfgp_handle_t h, int nlf, int n, int p, int d, const void* cache,
-                                    size_t cache_bytes, const double* Xall, int ldx, int nref, int ncand,
-                                    const double* w, const double* E, int ldE, int k, void* ws, size_t ws_bytes,
-                                    double* score, int refresh) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (!design_geometry_ok(nlf, n, p, nref, ncand) || k < 0 || k > DESIGN_MAXQ) return MFGP_ERR_ARG;
-    if (ncand == 0) return MFGP_OK;
-    if (!cache || !Xall || !ws || !score || ldx < d + 1 || (k > 0 && (!E || ldE < nref + ncand))) return MFGP_ERR_ARG;
-    if (nref == 0) {   // nothing to buy down: zeros, after the same size checks as any other call
-        const GprCache c = gpr_cache_layout(h->nb, nlf, n, p, d, nullptr);
-        if (cache_bytes < c.bytes || ws_bytes < design_layout(h->nb, c.T, c.Tp, p, nref, ncand, nullptr).bytes)
-            return MFGP_ERR_WORKSPACE;
-        (void)hipMemsetAsync(score, 0, sizeof(double) * (size_t)ncand, h->stream);
-        return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
-    }
-    double* Em = const_cast<double*>(E);   // (only read in this mode)
-    if (h->nb == 64)
-        return gpr_posterior_design_impl<64>(h, nlf, n, p, d, cache, cache_bytes, Xall, ldx, nref, ncand, w, Em, ldE,
-                                             k, ws, ws_bytes, score, refresh, nullptr);
-    return gpr_posterior_design_impl<32>(h, nlf, n, p, d, cache, cache_bytes, Xall, ldx, nref, ncand, w, Em, ldE, k, ws,
-                                         ws_bytes, score, refresh, nullptr);
-}
-
-int mfgp_gpr_posterior_design_append(mfgp_handle_t h, int nlf, int n, int p, int d, const void* cache,
-                                     size_t cache_bytes, const double* Xall, int ldx, int nref, int ncand, void* ws,
-                                     size_t ws_bytes, const int* pick, double* E, int ldE, int k) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (!design_geometry_ok(nlf, n, p, nref, ncand) || k < 0 || k >= DESIGN_MAXQ) return MFGP_ERR_ARG;
-    if (ncand == 0) return MFGP_OK;
-    if (!cache || !Xall || !ws || !pick || !E || ldx < d + 1 || ldE < nref + ncand) return MFGP_ERR_ARG;
-    if (h->nb == 64)
-        return gpr_posterior_design_impl<64>(h, nlf, n, p, d, cache, cache_bytes, Xall, ldx, nref, ncand, nullptr, E,
-                                             ldE, k, ws, ws_bytes, nullptr, 0, pick);
-    return gpr_posterior_design_impl<32>(h, nlf, n, p, d, cache, cache_bytes, Xall, ldx, nref, ncand, nullptr, E, ldE, k,
-                                         ws, ws_bytes, nullptr, 0, pick);
-}
-
-int mfgp_svgp_posterior_size(mfgp_handle_t h, int m, int l, int p, int d, size_t* bytes) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (m < 1 || l < 1 || p < 1 || !bytes) return MFGP_ERR_ARG;
-    *bytes = svgp_cache_layout(h->nb, m, l, p, d, nullptr).bytes;
-    return MFGP_OK;
-}
-
-int mfgp_svgp_posterior_build(mfgp_handle_t h, int m, int l, int p, int d, const double* Z, int ldz,
-                              const double* thetas, const double* q_mu, const double* q_sqrt, const double* W,
-                              double jitter, void* ws, size_t ws_bytes, void* cache, size_t cache_bytes, int* info) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (m < 1 || l < 1 || p < 1 || !Z || !thetas || !q_mu || !q_sqrt || !ws || !cache || !info || ldz < d + 1)
-        return MFGP_ERR_ARG;
-    if (!W && l != p) return MFGP_ERR_ARG;
-    return svgp_posterior_build_impl(h, m, l, p, d, Z, ldz, thetas, q_mu, q_sqrt, W, jitter, ws, ws_bytes, cache,
-                                     cache_bytes, info);
-}
-
-int mfgp_svgp_posterior_predict_workspace_size(mfgp_handle_t h, int nstar, int m, int l, int p, int d, size_t* bytes) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (nstar < 1 || m < 1 || l < 1 || p < 1 || !bytes) return MFGP_ERR_ARG;
-    *bytes = post_layout(h->nb, ceil_div(m, h->nb), 0, nstar, l, true, nullptr).bytes;
-    return MFGP_OK;
-}
-
-int mfgp_svgp_posterior_predict(mfgp_handle_t h, int nstar, int m, int l, int p, int d, int mixed, const void* cache,
-                                size_t cache_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes,
-                                double* f_mu, double* f_var) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (nstar < 1 || m < 1 || l < 1 || p < 1 || !cache || !Xs || !ws || !f_mu || !f_var || ldxs < d + 1)
-        return MFGP_ERR_ARG;
-    if (!mixed && l != p) return MFGP_ERR_ARG;
-    return svgp_posterior_predict_impl(h, nstar, m, l, p, d, mixed, cache, cache_bytes, Xs, ldxs, ws, ws_bytes, f_mu,
-                                       f_var);
-}
-
-int mfgp_svgp_posterior_predict_vjp_workspace_size(mfgp_handle_t h, int nstar, int m, int l, int p, int d,
-                                                   size_t* bytes) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (nstar < 1 || m < 1 || l < 1 || p < 1 || !bytes) return MFGP_ERR_ARG;
-    const int T = ceil_div(m, h->nb);
-    const PostLayout P = post_layout(h->nb, T, 0, nstar, l, true, nullptr);
-    *bytes = post_grad_layout(h->nb, P, T, d, l, true, nullptr).bytes;
-    return MFGP_OK;
-}
-
-int mfgp_svgp_posterior_predict_vjp(mfgp_handle_t h, int nstar, int m, int l, int p, int d, int mixed,
-                                    const void* cache, size_t cache_bytes, const double* Xs, int ldxs, void* ws,
-                                    size_t ws_bytes, double* f_mu, double* f_var, const double* gmean, int ldgm,
-                                    const double* gvar, double* gX, int ldgx) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (nstar == 0) return MFGP_OK;
-    if (nstar < 0 || m < 1 || l < 1 || p < 1 || !cache || !Xs || !ws || !f_mu || !f_var || !gX || ldxs < d + 1 ||
-        ldgx < d + 1)
-        return MFGP_ERR_ARG;
-    if (!mixed && l != p) return MFGP_ERR_ARG;
-    if (gmean && ldgm < p) return MFGP_ERR_ARG;
-    const PostGradIO g{gmean, ldgm, gvar, gX, ldgx};
-    return svgp_posterior_predict_impl(h, nstar, m, l, p, d, mixed, cache, cache_bytes, Xs, ldxs, ws, ws_bytes, f_mu,
-                                       f_var, &g);
 }
 
 int mfgp_selftest_mfma(mfgp_handle_t h, double* out) {

@@ -556,6 +556,122 @@ class Engine:
                                              ptr(info)), "mfgp_svgp_predict_cov")
         return f_mu, f_cov, info
 
+    # ---- cached posterior (posteriors.py).  `cache` is the uint8 device block its caller owns, `shape`
+    # what it was built for: GPR (n, p, d), SVGP (m, L, p, d, mixed).  The calls behind the two builds
+    # read only that block and their arguments: no parameter upload, no host read of a device word.
+    def gpr_posterior_bytes(self, nlf, n, p, d) -> int:
+        return self._size(self.lib.mfgp_gpr_posterior_size, nlf, n, p, d)
+
+    def gpr_posterior_build(self, nlf, X, Y, theta, cache):
+        """Fill `cache` (>= gpr_posterior_bytes) from the data and theta; returns the factorization's info [1]."""
+        n, dp1 = X.shape
+        p, d = Y.shape[1], dp1 - 1
+        ws = self.workspace("pred_cov", self._size(self.lib.mfgp_gpr_predict_cov_workspace_size, nlf, n, p, d, 1))
+        info = torch.empty((1,), dtype=torch.int32, device=self.device)
+        check(self.lib.mfgp_gpr_posterior_build(self.h, nlf, n, p, d, ptr(X), dp1, ptr(Y), p, ptr(theta), ptr(ws),
+                                                ws.numel(), ptr(cache), cache.numel(), ptr(info)),
+              "mfgp_gpr_posterior_build")
+        return info
+
+    def gpr_posterior_predict(self, nlf, shape, cache, Xs, full_cov=False, grad=None, out=None):
+        """(mean [ns, p], var [ns], third): third is cov [ns, ns] with full_cov, else None.  grad =
+        (grad_mean [ns, p], grad_var [ns]), either may be None (zero): the VJP call, third is the gradient
+        w.r.t. Xs [ns, d + 1].  out: the three result tensors, preallocated."""
+        n, p, d = shape
+        ns = Xs.shape[0]
+        if out is None:
+            f64 = dict(dtype=torch.float64, device=self.device)
+            third = (ns, d + 1) if grad is not None else (ns, ns) if full_cov else None
+            out = (torch.empty((ns, p), **f64), torch.empty((ns,), **f64),
+                   None if third is None else torch.empty(third, **f64))
+        mean, var, third = out
+        if ns == 0:
+            return out
+        # the two entries share their arguments up to var; then cov, ldc / gmean, ldgm, gvar, gX, ldgx
+        name = "mfgp_gpr_posterior_predict" if grad is None else "mfgp_gpr_posterior_predict_vjp"
+        tail = (ptr(third), ns) if grad is None else (ptr(grad[0]), p, ptr(grad[1]), ptr(third), d + 1)
+        ws = self.workspace("post_pred" if grad is None else "post_vjp",
+                            self._size(getattr(self.lib, name + "_workspace_size"), nlf, n, p, d, ns))
+        check(getattr(self.lib, name)(self.h, nlf, n, p, d, ns, ptr(cache), cache.numel(), ptr(Xs), Xs.shape[1],
+                                      ptr(ws), ws.numel(), ptr(mean), p, ptr(var), *tail), name)
+        return out
+
+    def gpr_posterior_leave_out(self, nlf, shape, cache, offsets, rows, gmax, out=None):
+        """Leave-group-out from the cache: int32 device offsets [G + 1] and rows [R] (group g is
+        rows[offsets[g]:offsets[g + 1]], at most gmax rows) -> (resid [R, p], cov [R, gmax], logdens [G, p],
+        info [G]).  out: those four, preallocated."""
+        n, p, d = shape
+        ng, nr = offsets.shape[0] - 1, rows.shape[0]
+        if out is None:
+            f64 = dict(dtype=torch.float64, device=self.device)
+            out = (torch.empty((nr, p), **f64), torch.empty((nr, gmax), **f64), torch.empty((ng, p), **f64),
+                   torch.empty((ng,), dtype=torch.int32, device=self.device))
+        resid, cov, logd, info = out
+        ws = self.workspace("post_lo", self._size(self.lib.mfgp_gpr_posterior_leave_out_workspace_size, nlf, n, p, d,
+                                                  ng, nr))
+        check(self.lib.mfgp_gpr_posterior_leave_out(self.h, nlf, n, p, d, ptr(cache), cache.numel(), ng, ptr(offsets),
+                                                    ptr(rows), nr, gmax, ptr(ws), ws.numel(), ptr(resid), p, ptr(cov),
+                                                    gmax, ptr(logd), ptr(info)), "mfgp_gpr_posterior_leave_out")
+        return out
+
+    def gpr_posterior_design_workspace(self, nlf, shape, nref, ncand, qmax) -> torch.Tensor:
+        """The workspace of one batch of design calls (it carries the forward's A from score step 0 on)."""
+        n, p, d = shape
+        return self.workspace("post_design", self._size(self.lib.mfgp_gpr_posterior_design_workspace_size, nlf, n, p,
+                                                        d, nref, ncand, qmax))
+
+    def gpr_posterior_design_score(self, nlf, shape, cache, Xall, nref, w, E, k, ws):
+        """score [ncand] of the candidates Xall[nref:] over the references Xall[:nref] (weights w or None),
+        conditioned on the k rows of E; k == 0 runs the forward on Xall first."""
+        n, p, d = shape
+        nall = Xall.shape[0]
+        score = torch.empty((nall - nref,), dtype=torch.float64, device=self.device)
+        check(self.lib.mfgp_gpr_posterior_design_score(self.h, nlf, n, p, d, ptr(cache), cache.numel(), ptr(Xall),
+                                                       d + 1, nref, nall - nref, ptr(w), ptr(E), nall, k, ptr(ws),
+                                                       ws.numel(), ptr(score), 1 if k == 0 else 0),
+              "mfgp_gpr_posterior_design_score")
+        return score
+
+    def gpr_posterior_design_append(self, nlf, shape, cache, Xall, nref, pick, E, k, ws):
+        """Row k of E: the conditioning row of the candidate whose index the int32 device word `pick` holds."""
+        n, p, d = shape
+        nall = Xall.shape[0]
+        check(self.lib.mfgp_gpr_posterior_design_append(self.h, nlf, n, p, d, ptr(cache), cache.numel(), ptr(Xall),
+                                                        d + 1, nref, nall - nref, ptr(ws), ws.numel(), ptr(pick),
+                                                        ptr(E), nall, k), "mfgp_gpr_posterior_design_append")
+
+    def svgp_posterior_bytes(self, m, L, p, d) -> int:
+        return self._size(self.lib.mfgp_svgp_posterior_size, m, L, p, d)
+
+    def svgp_posterior_build(self, Z, thetas, q_mu, q_sqrt, W, p, jitter, cache):
+        """Fill `cache` (>= svgp_posterior_bytes) from the variational state; returns the K_uu factorizations' info [L]."""
+        m, dp1 = Z.shape
+        d, L = dp1 - 1, thetas.shape[0]
+        ws = self.workspace("svgp_pred", self._size(self.lib.mfgp_svgp_workspace_size, 1, m, L, p, d))
+        info = torch.empty((L,), dtype=torch.int32, device=self.device)
+        check(self.lib.mfgp_svgp_posterior_build(self.h, m, L, p, d, ptr(Z), dp1, ptr(thetas), ptr(q_mu), ptr(q_sqrt),
+                                                 ptr(W), float(jitter), ptr(ws), ws.numel(), ptr(cache), cache.numel(),
+                                                 ptr(info)), "mfgp_svgp_posterior_build")
+        return info
+
+    def svgp_posterior_predict(self, shape, cache, Xs, grad=None):
+        """(f_mu [ns, p], f_var [ns, p], None); grad = (grad_mean, grad_var), each [ns, p] or None (zero):
+        the VJP call, third is the gradient w.r.t. Xs [ns, d + 1]."""
+        m, L, p, d, mixed = shape
+        ns = Xs.shape[0]
+        f64 = dict(dtype=torch.float64, device=self.device)
+        f_mu, f_var = torch.empty((ns, p), **f64), torch.empty((ns, p), **f64)
+        gX = None if grad is None else torch.empty((ns, d + 1), **f64)
+        if ns == 0:
+            return f_mu, f_var, gX
+        name = "mfgp_svgp_posterior_predict" if grad is None else "mfgp_svgp_posterior_predict_vjp"
+        tail = () if grad is None else (ptr(grad[0]), p, ptr(grad[1]), ptr(gX), d + 1)
+        ws = self.workspace("post_pred" if grad is None else "post_vjp",
+                            self._size(getattr(self.lib, name + "_workspace_size"), ns, m, L, p, d))
+        check(getattr(self.lib, name)(self.h, ns, m, L, p, d, 1 if mixed else 0, ptr(cache), cache.numel(), ptr(Xs),
+                                      Xs.shape[1], ptr(ws), ws.numel(), ptr(f_mu), ptr(f_var), *tail), name)
+        return f_mu, f_var, gX
+
     def selftest_mfma(self) -> np.ndarray:
         out = torch.zeros((16, 16), dtype=torch.float64, device=self.device)
         check(self.lib.mfgp_selftest_mfma(self.h, ptr(out)), "mfgp_selftest_mfma")

@@ -29,7 +29,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 import torch
 
-from ._lib import MFGPError, check, info_error, ptr
+from ._lib import MFGPError, info_error
 from .engine import Engine, to_dev
 from .params import as_result
 from .session import CholeskyError
@@ -228,7 +228,7 @@ class _PredictFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_mean, grad_var):
         (Xnew,) = ctx.saved_tensors
-        _, _, gX = ctx.post._vjp(ctx.cache, Xnew, grad_mean, grad_var)
+        _, _, gX = ctx.post._predict(ctx.cache, Xnew, grad=(grad_mean, grad_var))
         return gX.to(device=Xnew.device, dtype=Xnew.dtype), None
 
 
@@ -283,11 +283,10 @@ class _Posterior:
         ``grad_mean`` / ``grad_var`` are [N*, P] (None: zero; GPR also takes ``grad_var`` [N*], the
         gradient w.r.t. the one variance column that predict_f tiles over P).  mean / var carry
         predict_f's bits.  Like predict_f it is the snapshot's until update_cache()."""
-        if self._precompute_cache is PrecomputeCacheType.NOCACHE:
-            raise NotImplementedError("predict_f_vjp: a NOCACHE posterior has no cached factors to differentiate "
-                                      "through; use a TENSOR or VARIABLE cache")
+        self._need_cache("predict_f_vjp: a NOCACHE posterior has no cached factors to differentiate through; use a "
+                         "TENSOR or VARIABLE cache")
         self._check_vjp()
-        mean, var, gX = self._vjp(self.cache, Xnew, grad_mean, grad_var)
+        mean, var, gX = self._predict(self.cache, Xnew, grad=(grad_mean, grad_var))
         return as_result(mean), as_result(var), as_result(gX)
 
     def _check_vjp(self):
@@ -295,12 +294,27 @@ class _Posterior:
 
     def _attached(self, Xnew):
         """predict_f of a requires_grad Xnew: outputs attached to autograd (backward = the VJP call)."""
-        if self._precompute_cache is PrecomputeCacheType.NOCACHE:
-            raise NotImplementedError("predict_f of an Xnew that requires grad needs a cached posterior "
-                                      "(TENSOR or VARIABLE)")
+        self._need_cache("predict_f of an Xnew that requires grad needs a cached posterior (TENSOR or VARIABLE)")
         self._check_vjp()
         mean, var = _PredictFn.apply(Xnew, self)
         return as_result(mean), as_result(var)
+
+    def _marginal(self, Xnew):
+        mean, var = self.predict_f(Xnew.detach())
+        return mean.as_subclass(torch.Tensor), var.as_subclass(torch.Tensor)
+
+    def _need_cache(self, nocache: str):
+        """The first line of every call that only a cache can serve."""
+        if self._precompute_cache is PrecomputeCacheType.NOCACHE:
+            raise NotImplementedError(nocache)
+
+    def _engine(self, cache=None) -> Engine:
+        """The engine of the device the cache block lives on (`cache`: the block an autograd node kept;
+        None: the current one), after the check that the block can be used."""
+        cache = self.cache if cache is None else cache
+        eng = Engine.get(cache.device if cache is not None else None)
+        self._require_cache(eng)
+        return eng
 
     def _require_cache(self, eng: Engine):
         if not self._valid:
@@ -325,15 +339,9 @@ class GPRPosterior(_Posterior):
     def _build(self):
         eng, X, Y = self.model._device_data()
         theta = torch.tensor(self._theta_fn(), dtype=torch.float64, device=eng.device)
-        n, dp1 = X.shape
-        p, d, nlf = Y.shape[1], dp1 - 1, self._nlf
-        lib = eng.lib
-        nbytes = eng._size(lib.mfgp_gpr_posterior_size, nlf, n, p, d)
-        ws = eng.workspace("pred_cov", eng._size(lib.mfgp_gpr_predict_cov_workspace_size, nlf, n, p, d, 1))
-        buf = self._cache_buffer(eng, nbytes)
-        info = torch.empty((1,), dtype=torch.int32, device=eng.device)
-        check(lib.mfgp_gpr_posterior_build(eng.h, nlf, n, p, d, ptr(X), dp1, ptr(Y), p, ptr(theta), ptr(ws),
-                                           ws.numel(), ptr(buf), buf.numel(), ptr(info)), "mfgp_gpr_posterior_build")
+        n, p, d = X.shape[0], Y.shape[1], X.shape[1] - 1
+        buf = self._cache_buffer(eng, eng.gpr_posterior_bytes(self._nlf, n, p, d))
+        info = eng.gpr_posterior_build(self._nlf, X, Y, theta, buf)
         self._shape, self._nb = (n, p, d), eng.tile()
         self._commit(buf, info, "posterior")
 
@@ -349,24 +357,28 @@ class GPRPosterior(_Posterior):
             return self._attached(Xnew)
         if self._precompute_cache is PrecomputeCacheType.NOCACHE:
             return self.fused_predict_f(Xnew, full_cov=full_cov)
-        eng = Engine.get(self.cache.device if self.cache is not None else None)
-        self._require_cache(eng)
-        n, p, d = self._shape
+        mean, var, _ = self._predict(self.cache, Xnew, full_cov=full_cov)
+        return as_result(mean), as_result(var)
+
+    def _predict(self, cache, Xnew, full_cov=False, grad=None):
+        """predict_f on `cache`: (mean, var or cov tiled over P, None); with grad = (grad_mean, grad_var) the
+        VJP call: (mean, var, grad_X)."""
+        eng = self._engine(cache)
+        p = self._shape[1]
         Xs = to_dev(Xnew, eng.device)
-        ns = Xs.shape[0]
-        f64 = dict(dtype=torch.float64, device=eng.device)
-        mean, var = torch.empty((ns, p), **f64), torch.empty((ns,), **f64)
-        cov = torch.empty((ns, ns), **f64) if full_cov else None
-        if ns:
-            lib = eng.lib
-            ws = eng.workspace("post_pred", eng._size(lib.mfgp_gpr_posterior_predict_workspace_size, self._nlf, n, p,
-                                                      d, ns))
-            check(lib.mfgp_gpr_posterior_predict(eng.h, self._nlf, n, p, d, ns, ptr(self.cache), self.cache.numel(),
-                                                 ptr(Xs), Xs.shape[1], ptr(ws), ws.numel(), ptr(mean), p, ptr(var),
-                                                 ptr(cov), ns), "mfgp_gpr_posterior_predict")
+        if grad is not None:
+            ns = Xs.shape[0]
+            gm, gv = _upstream(grad[0], (ns, p), eng.device, "grad_mean"), grad[1]
+            if gv is not None:
+                gv = to_dev(gv, eng.device)
+                if gv.dim() == 2:   # the variance is one column tiled over P: its upstream gradients add up
+                    gv = _upstream(gv, (ns, p), eng.device, "grad_var").sum(dim=1)
+                gv = _upstream(gv, (ns,), eng.device, "grad_var")
+            grad = (gm, gv)
+        mean, var, third = eng.gpr_posterior_predict(self._nlf, self._shape, cache, Xs, full_cov, grad)
         if full_cov:
-            return as_result(mean), as_result(cov[None].expand(p, -1, -1).contiguous())
-        return as_result(mean), as_result(var[:, None].expand(-1, p).contiguous())
+            return mean, third[None].expand(p, -1, -1).contiguous(), None
+        return mean, var[:, None].expand(-1, p).contiguous(), third
 
     def leave_out(self, groups=None, full_cov: bool = False) -> LeaveOutResult:
         """Leave-group-out cross-validation at the snapshot's hyper-parameters: for every group of
@@ -382,13 +394,10 @@ class GPRPosterior(_Posterior):
         the kernel's 1e-6 jitter is part of K and stays in the covariance).  With an asymmetric
         ``rho_LF`` a refit's ``predict_f`` at a row of LF source j >= 1 takes its cross-covariance from
         the other triangle and is another model there; rows of source 0 and HF rows agree with it."""
-        if self._precompute_cache is PrecomputeCacheType.NOCACHE:
-            raise NotImplementedError("leave_out: a NOCACHE posterior has no cached factors; use a TENSOR or "
-                                      "VARIABLE cache")
-        eng = Engine.get(self.cache.device if self.cache is not None else None)
-        self._require_cache(eng)
+        self._need_cache("leave_out: a NOCACHE posterior has no cached factors; use a TENSOR or VARIABLE cache")
         n, p, d = self._shape
-        offsets, rows, gmax = normalize_groups(groups, n)   # every ValueError is raised before any launch
+        offsets, rows, gmax = normalize_groups(groups, n)   # every ValueError is raised before the device is touched
+        eng = self._engine()
         ng, nr = offsets.shape[0] - 1, rows.shape[0]
         group = np.repeat(np.arange(ng, dtype=np.int64), np.diff(offsets))
         pos = np.arange(nr, dtype=np.int64) - offsets[:-1].astype(np.int64)[group]   # place inside the group
@@ -399,15 +408,7 @@ class GPRPosterior(_Posterior):
                                   z(0, 0, 0) if full_cov else None)
         idx = torch.from_numpy(np.concatenate([offsets, rows, pos.astype(np.int32)])).to(eng.device)
         d_off, d_rows, d_pos = idx[:ng + 1], idx[ng + 1:ng + 1 + nr], idx[ng + 1 + nr:].long()
-        resid, cov = torch.empty((nr, p), **f64), torch.empty((nr, gmax), **f64)
-        logd = torch.empty((ng, p), **f64)
-        info = torch.empty((ng,), dtype=torch.int32, device=eng.device)
-        lib = eng.lib
-        ws = eng.workspace("post_lo", eng._size(lib.mfgp_gpr_posterior_leave_out_workspace_size, self._nlf, n, p, d,
-                                                ng, nr))
-        check(lib.mfgp_gpr_posterior_leave_out(eng.h, self._nlf, n, p, d, ptr(self.cache), self.cache.numel(), ng,
-                                               ptr(d_off), ptr(d_rows), nr, gmax, ptr(ws), ws.numel(), ptr(resid), p,
-                                               ptr(cov), gmax, ptr(logd), ptr(info)), "mfgp_gpr_posterior_leave_out")
+        resid, cov, logd, info = eng.gpr_posterior_leave_out(self._nlf, self._shape, self.cache, d_off, d_rows, gmax)
         Y = self.model._device_data()[2]   # the construction-time targets (they cannot be reassigned)
         mean = Y.index_select(0, d_rows) - resid
         var = cov.gather(1, d_pos[:, None]).expand(-1, p).contiguous()
@@ -454,10 +455,8 @@ class GPRPosterior(_Posterior):
         return self._design(Xcand, Xref, weights, cost, q, "select")
 
     def _design(self, Xcand, Xref, weights, cost, q, what):
-        if self._precompute_cache is PrecomputeCacheType.NOCACHE:
-            raise NotImplementedError(f"{what}: a NOCACHE posterior has no cached factors; use a TENSOR or "
-                                      "VARIABLE cache")
-        n, p, d = self._shape
+        self._need_cache(f"{what}: a NOCACHE posterior has no cached factors; use a TENSOR or VARIABLE cache")
+        d = self._shape[2]
         nc, nr = _design_rows(Xcand, d, f"{what}: Xcand"), _design_rows(Xref, d, f"{what}: Xref")
         w = _design_vector(weights, nr, f"{what}: weights", False)
         cost = _design_vector(cost, nc, f"{what}: cost", True)
@@ -467,8 +466,7 @@ class GPRPosterior(_Posterior):
             if nc == 0:
                 raise ValueError(f"{what}: no candidate to pick from (Xcand has no rows)")
             q = int(q)
-        eng = Engine.get(self.cache.device if self.cache is not None else None)   # every ValueError is raised above
-        self._require_cache(eng)
+        eng = self._engine()   # every ValueError is raised above
         f64 = dict(dtype=torch.float64, device=eng.device)
         if cost is not None:
             cost = cost.to(eng.device)
@@ -481,63 +479,26 @@ class GPRPosterior(_Posterior):
         Xall = torch.cat([to_dev(Xref, eng.device), to_dev(Xcand, eng.device)]).contiguous()
         w = None if w is None else w.to(eng.device).contiguous()
         nall, steps = nr + nc, 1 if q is None else q
-        lib, nlf = eng.lib, self._nlf
-        ws = eng.workspace("post_design", eng._size(lib.mfgp_gpr_posterior_design_workspace_size, nlf, n, p, d, nr, nc,
-                                                    steps))
+        call = (self._nlf, self._shape, self.cache, Xall, nr)
+        ws = eng.gpr_posterior_design_workspace(self._nlf, self._shape, nr, nc, steps)
         E = torch.empty((steps - 1, nall), **f64) if steps > 1 else None
         picks = torch.empty((steps,), dtype=torch.int64, device=eng.device)
         gain = torch.empty((steps,), **f64)
         for k in range(steps):
-            score = torch.empty((nc,), **f64)
-            check(lib.mfgp_gpr_posterior_design_score(eng.h, nlf, n, p, d, ptr(self.cache), self.cache.numel(),
-                                                      ptr(Xall), d + 1, nr, nc, ptr(w), ptr(E), nall, k, ptr(ws),
-                                                      ws.numel(), ptr(score), 1 if k == 0 else 0),
-                  "mfgp_gpr_posterior_design_score")
+            score = eng.gpr_posterior_design_score(*call, w, E, k, ws)
             if q is None:
                 return as_result(score)
             idx = torch.argmax(score if cost is None else score / cost)
             picks[k] = idx
             gain[k:k + 1] = score.index_select(0, idx.reshape(1))   # score[idx] would read idx on the host
             if k + 1 < steps:
-                pick = idx.to(torch.int32)
-                check(lib.mfgp_gpr_posterior_design_append(eng.h, nlf, n, p, d, ptr(self.cache), self.cache.numel(),
-                                                           ptr(Xall), d + 1, nr, nc, ptr(ws), ws.numel(), ptr(pick),
-                                                           ptr(E), nall, k), "mfgp_gpr_posterior_design_append")
+                eng.gpr_posterior_design_append(*call, idx.to(torch.int32), E, k, ws)
         return DesignResult(as_result(picks), as_result(gain))
-
-    def _marginal(self, Xnew):
-        mean, var = self.predict_f(Xnew.detach())
-        return mean.as_subclass(torch.Tensor), var.as_subclass(torch.Tensor)
 
     def _check_vjp(self):
         if self._nlf:
             raise NotImplementedError("predict_f_vjp: the graph kernel's input gradient (a derivative per source) "
                                       "is not built; only the linear multi-fidelity kernel has one")
-
-    def _vjp(self, cache, Xnew, grad_mean, grad_var):
-        eng = Engine.get(cache.device if cache is not None else None)
-        self._require_cache(eng)
-        n, p, d = self._shape
-        Xs = to_dev(Xnew, eng.device)
-        ns = Xs.shape[0]
-        gm = _upstream(grad_mean, (ns, p), eng.device, "grad_mean")
-        gv = None
-        if grad_var is not None:
-            gv = to_dev(grad_var, eng.device)
-            if gv.dim() == 2:   # the variance is one column tiled over P: its upstream gradients add up
-                gv = _upstream(gv, (ns, p), eng.device, "grad_var").sum(dim=1)
-            gv = _upstream(gv, (ns,), eng.device, "grad_var")
-        f64 = dict(dtype=torch.float64, device=eng.device)
-        mean, var = torch.empty((ns, p), **f64), torch.empty((ns,), **f64)
-        gX = torch.empty((ns, d + 1), **f64)   # every entry is written by the call (fidelity column: 0)
-        if ns:
-            lib = eng.lib
-            ws = eng.workspace("post_vjp", eng._size(lib.mfgp_gpr_posterior_predict_vjp_workspace_size, self._nlf, n,
-                                                     p, d, ns))
-            check(lib.mfgp_gpr_posterior_predict_vjp(eng.h, self._nlf, n, p, d, ns, ptr(cache), cache.numel(), ptr(Xs),
-                                                     Xs.shape[1], ptr(ws), ws.numel(), ptr(mean), p, ptr(var), ptr(gm),
-                                                     p, ptr(gv), ptr(gX), d + 1), "mfgp_gpr_posterior_predict_vjp")
-        return mean, var[:, None].expand(-1, p).contiguous(), gX
 
 
 class SVGPPosterior(_Posterior):
@@ -557,16 +518,9 @@ class SVGPPosterior(_Posterior):
 
     def _build(self):
         eng, Z, thetas, q_mu, q_sqrt, W = self.model._dev_state()
-        m, dp1 = Z.shape
-        d, L, p = dp1 - 1, thetas.shape[0], int(self.model.num_outputs)
-        lib = eng.lib
-        nbytes = eng._size(lib.mfgp_svgp_posterior_size, m, L, p, d)
-        ws = eng.workspace("svgp_pred", eng._size(lib.mfgp_svgp_workspace_size, 1, m, L, p, d))
-        buf = self._cache_buffer(eng, nbytes)
-        info = torch.empty((L,), dtype=torch.int32, device=eng.device)
-        check(lib.mfgp_svgp_posterior_build(eng.h, m, L, p, d, ptr(Z), dp1, ptr(thetas), ptr(q_mu), ptr(q_sqrt),
-                                            ptr(W), self._jitter, ptr(ws), ws.numel(), ptr(buf), buf.numel(),
-                                            ptr(info)), "mfgp_svgp_posterior_build")
+        m, d, L, p = Z.shape[0], Z.shape[1] - 1, thetas.shape[0], int(self.model.num_outputs)
+        buf = self._cache_buffer(eng, eng.svgp_posterior_bytes(m, L, p, d))
+        info = eng.svgp_posterior_build(Z, thetas, q_mu, q_sqrt, W, p, self._jitter, buf)
         self._shape, self._nb = (m, L, p, d, W is not None), eng.tile()
         self._state = (Z, thetas, q_mu, q_sqrt, W)   # the snapshot the covariance forms run on
         self._commit(buf, info, "posterior")
@@ -581,49 +535,25 @@ class SVGPPosterior(_Posterior):
             return self._attached(Xnew)
         if self._precompute_cache is PrecomputeCacheType.NOCACHE:
             return self.fused_predict_f(Xnew, full_cov=full_cov, full_output_cov=full_output_cov)
-        eng = Engine.get(self.cache.device if self.cache is not None else None)
-        self._require_cache(eng)
-        m, L, p, d, mixed = self._shape
-        Xs = to_dev(Xnew, eng.device)
         if full_cov or full_output_cov:
+            eng = self._engine()
             mode = 3 if (full_cov and full_output_cov) else (1 if full_cov else 2)
             Z, thetas, q_mu, q_sqrt, W = self._state
-            f_mu, f_cov, info = eng.svgp_predict_cov(mode, Xs, Z, thetas, q_mu, q_sqrt, W, p, self._jitter)
+            f_mu, f_cov, info = eng.svgp_predict_cov(mode, to_dev(Xnew, eng.device), Z, thetas, q_mu, q_sqrt, W,
+                                                     self._shape[2], self._jitter)
             if int(info.max().item()) != 0:
                 raise CholeskyError("predict_f: Cholesky of K_uu was not successful")
             return as_result(f_mu), as_result(f_cov)
-        ns = Xs.shape[0]
-        f64 = dict(dtype=torch.float64, device=eng.device)
-        f_mu, f_var = torch.empty((ns, p), **f64), torch.empty((ns, p), **f64)
-        if ns:
-            lib = eng.lib
-            ws = eng.workspace("post_pred", eng._size(lib.mfgp_svgp_posterior_predict_workspace_size, ns, m, L, p, d))
-            check(lib.mfgp_svgp_posterior_predict(eng.h, ns, m, L, p, d, 1 if mixed else 0, ptr(self.cache),
-                                                  self.cache.numel(), ptr(Xs), Xs.shape[1], ptr(ws), ws.numel(),
-                                                  ptr(f_mu), ptr(f_var)), "mfgp_svgp_posterior_predict")
+        f_mu, f_var, _ = self._predict(self.cache, Xnew)
         return as_result(f_mu), as_result(f_var)
 
-    def _marginal(self, Xnew):
-        f_mu, f_var = self.predict_f(Xnew.detach())
-        return f_mu.as_subclass(torch.Tensor), f_var.as_subclass(torch.Tensor)
-
-    def _vjp(self, cache, Xnew, grad_mean, grad_var):
-        eng = Engine.get(cache.device if cache is not None else None)
-        self._require_cache(eng)
-        m, L, p, d, mixed = self._shape
+    def _predict(self, cache, Xnew, grad=None):
+        """The marginal predict_f on `cache`: (f_mu, f_var, None); with grad = (grad_mean, grad_var) the VJP
+        call: (f_mu, f_var, grad_X)."""
+        eng = self._engine(cache)
         Xs = to_dev(Xnew, eng.device)
-        ns = Xs.shape[0]
-        gm = _upstream(grad_mean, (ns, p), eng.device, "grad_mean")
-        gv = _upstream(grad_var, (ns, p), eng.device, "grad_var")
-        f64 = dict(dtype=torch.float64, device=eng.device)
-        f_mu, f_var = torch.empty((ns, p), **f64), torch.empty((ns, p), **f64)
-        gX = torch.empty((ns, d + 1), **f64)   # every entry is written by the call (fidelity column: 0)
-        if ns:
-            lib = eng.lib
-            ws = eng.workspace("post_vjp", eng._size(lib.mfgp_svgp_posterior_predict_vjp_workspace_size, ns, m, L, p,
-                                                     d))
-            check(lib.mfgp_svgp_posterior_predict_vjp(eng.h, ns, m, L, p, d, 1 if mixed else 0, ptr(cache),
-                                                      cache.numel(), ptr(Xs), Xs.shape[1], ptr(ws), ws.numel(),
-                                                      ptr(f_mu), ptr(f_var), ptr(gm), p, ptr(gv), ptr(gX), d + 1),
-                  "mfgp_svgp_posterior_predict_vjp")
-        return f_mu, f_var, gX
+        if grad is not None:
+            shape = (Xs.shape[0], self._shape[2])
+            grad = (_upstream(grad[0], shape, eng.device, "grad_mean"),
+                    _upstream(grad[1], shape, eng.device, "grad_var"))
+        return eng.svgp_posterior_predict(self._shape, cache, Xs, grad)

@@ -301,7 +301,7 @@ def test_svgp_posterior_other_likelihoods(lik, hbs, eng):
 
 
 # ---------------------------------------------------------------- the schedules of the cached predict
-# post_chunk (mfgp_capi.hip) cuts rows into 8-tile tasks unless batch T Ts >= 256; the shapes below
+# post_chunk (mfgp_posterior_capi.hip) cuts rows into 8-tile tasks unless batch T Ts >= 256; the shapes below
 # reach each side for triangular (GPR) and square (SVGP) rows, more than 8 partials a row, more than
 # 8 row groups, a partial last batch of the mixing loop and the graph kernel with several row groups.
 # tests/test_posterior_host.py::test_posterior_shapes_reach_their_schedule witnesses on the host that

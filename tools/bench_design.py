@@ -29,7 +29,6 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-from multi_fidelity_gpflow_amd._lib import check, ptr   # noqa: E402
 from multi_fidelity_gpflow_amd.engine import Engine   # noqa: E402
 from oracle.mfgp_oracle import load_powerspecs   # noqa: E402
 from bench_leave_out import initial_model   # noqa: E402
@@ -65,15 +64,10 @@ def main():
     Xall = torch.cat([Xref, Xcand]).contiguous()
     nall = nr + nc
     f64 = dict(dtype=torch.float64, device=eng.device)
-    lib = eng.lib
-    mean, var, cov = torch.empty((nall, p), **f64), torch.empty((nall,), **f64), torch.empty((nall, nall), **f64)
+    bufs = torch.empty((nall, p), **f64), torch.empty((nall,), **f64), torch.empty((nall, nall), **f64)
 
     def block():
-        ws = eng.workspace("post_pred", eng._size(lib.mfgp_gpr_posterior_predict_workspace_size, 0, n, p, D, nall))
-        check(lib.mfgp_gpr_posterior_predict(eng.h, 0, n, p, D, nall, ptr(post.cache), post.cache.numel(), ptr(Xall),
-                                             D + 1, ptr(ws), ws.numel(), ptr(mean), p, ptr(var), ptr(cov), nall),
-              "mfgp_gpr_posterior_predict")
-        return cov
+        return eng.gpr_posterior_predict(0, (n, p, D), post.cache, Xall, full_cov=True, out=bufs)[2]
 
     def reduce(S):
         C = S[:nr, nr:]

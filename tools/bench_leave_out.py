@@ -28,7 +28,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import multi_fidelity_gpflow_amd as M   # noqa: E402
-from multi_fidelity_gpflow_amd._lib import check, ptr   # noqa: E402
 from multi_fidelity_gpflow_amd.engine import Engine   # noqa: E402
 from multi_fidelity_gpflow_amd.posteriors import normalize_groups   # noqa: E402
 from oracle.mfgp_oracle import load_powerspecs   # noqa: E402
@@ -42,27 +41,17 @@ def initial_model(X, Y):
 
 
 def device_call(eng, post, groups):
-    """The C call alone (its two launches), the group table and the outputs already on the device: what
-    leave_out spends on the device, without the host's table, upload, output ops and info read."""
-    n, p, d = post._shape
-    offsets, rows, gmax = normalize_groups(groups, n)
+    """The engine call alone (the C call's two launches), the group table and the outputs already on the device:
+    what leave_out spends on the device, without the host's table, upload, output ops and info read."""
+    p = post._shape[1]
+    offsets, rows, gmax = normalize_groups(groups, post._shape[0])
     ng, nr = offsets.shape[0] - 1, rows.shape[0]
     dev = eng.device
     d_off, d_rows = torch.from_numpy(offsets).to(dev), torch.from_numpy(rows).to(dev)
     f64 = dict(dtype=torch.float64, device=dev)
-    resid, cov, logd = torch.empty((nr, p), **f64), torch.empty((nr, gmax), **f64), torch.empty((ng, p), **f64)
-    info = torch.empty((ng,), dtype=torch.int32, device=dev)
-    lib = eng.lib
-    ws = eng.workspace("post_lo", eng._size(lib.mfgp_gpr_posterior_leave_out_workspace_size, 0, n, p, d, ng, nr))
-    keep = (d_off, d_rows, resid, cov, logd, info, ws)
-
-    def call():
-        check(lib.mfgp_gpr_posterior_leave_out(eng.h, 0, n, p, d, ptr(post.cache), post.cache.numel(), ng, ptr(d_off),
-                                               ptr(d_rows), nr, gmax, ptr(ws), ws.numel(), ptr(resid), p, ptr(cov), gmax,
-                                               ptr(logd), ptr(info)), "mfgp_gpr_posterior_leave_out")
-        return keep
-
-    return call
+    out = (torch.empty((nr, p), **f64), torch.empty((nr, gmax), **f64), torch.empty((ng, p), **f64),
+           torch.empty((ng,), dtype=torch.int32, device=dev))
+    return lambda: eng.gpr_posterior_leave_out(0, post._shape, post.cache, d_off, d_rows, gmax, out=out)
 
 
 def main():
