@@ -235,7 +235,10 @@ int mfgp_potrf_inv(mfgp_handle_t h, int n, int batch, const double* A, int lda, 
  *   thetas [L][2d+4] per-latent constrained kernel parameters (noise entry unused),
  *   Z [M, d+1], q_mu [M, L], q_sqrt [L, M, M] (lower used), W [P, L] or NULL
  *   (identity mixing; requires L == P).  out = [elbo, KL, VE]; g_mu / g_var
- *   [L][N] receive the latent predictive moments. */
+ *   [L][N] receive the latent predictive moments.
+ * Leading dimensions, for this and every mfgp_svgp_elbo* entry below (value and gradient alike):
+ * X [n][ldx] and Z [m][ldz] with ldx, ldz >= d + 1, Y [n][ldy] with ldy >= p; anything shorter is
+ * MFGP_ERR_ARG before any device work. */
 int mfgp_svgp_workspace_size(mfgp_handle_t h, int n, int m, int l, int p, int d, size_t* bytes);
 int mfgp_svgp_elbo(mfgp_handle_t h, int n, int m, int l, int p, int d, const double* X, int ldx, const double* Y,
                    int ldy, const double* Z, int ldz, const double* thetas, const double* q_mu,

@@ -613,31 +613,10 @@ static int predict_impl(mfgp_handle_t h, int n, int p, int d, int nstar, const d
     return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
 }
 
-size_t svgp_workspace_bytes(int nb, int n, int m, int l, int p, int d);
-int svgp_elbo_impl(hipStream_t s, int nb, int n, int m, int l, int p, int d, const double* X, int ldx,
-                   const double* Y, int ldy, const double* Z, int ldz, const double* thetas, const double* q_mu,
-                   const double* q_sqrt, const double* W, double noise, double scale, double jitter, void* ws,
-                   size_t ws_bytes, double* out, double* g_mu, double* g_var, int* info, const double* noise_dev);
-size_t svgp_grad_workspace_bytes(int nb, int n, int m, int l, int p, int d);
-int svgp_grad_impl(hipStream_t s, int nb, int n, int m, int l, int p, int d, const double* X, int ldx, const double* Y,
-                   int ldy, const double* Z, int ldz, const double* thetas, const double* q_mu, const double* q_sqrt,
-                   const double* W, const double* noise_dev, double noise_host, double scale, double kl_mult,
-                   double jitter, void* ws, size_t ws_bytes, double* out, double* g_mu, double* g_var, double* gZ,
-                   double* gtheta, double* gq_mu, double* gq_sqrt, double* gW, double* gnoise, int* info);
 int adam_packed_impl(hipStream_t st, int n, double* u, double* c, const double* g, double* m, double* v,
                      const unsigned char* trainable, const unsigned char* transform, const unsigned char* span,
                      int* step, const double* lr_sched, double b1, double b2, double eps, const double* out,
                      double klm, double* loss_hist, double* kl_hist, const int* info, int ninfo);
-
-size_t svgp_predict_cov_workspace_bytes(int nb, int ns, int m, int l, int p, int d);
-int svgp_predict_cov_impl(hipStream_t s, int nb, int mode, int ns, int m, int l, int p, int d, const double* Xs,
-                          int ldx, const double* Z, int ldz, const double* thetas, const double* q_mu,
-                          const double* q_sqrt, const double* W, double jitter, void* ws, size_t ws_bytes,
-                          double* g_mu, double* g_var, double* f_mu, double* f_var, double* f_cov, int* info);
-int svgp_predict_impl(hipStream_t s, int nb, int n, int m, int l, int p, int d, const double* Xs, int ldx,
-                      const double* Z, int ldz, const double* thetas, const double* q_mu, const double* q_sqrt,
-                      const double* W, double jitter, void* ws, size_t ws_bytes, double* g_mu, double* g_var,
-                      double* f_mu, double* f_var, int* info);
 
 // ---------------------------------------------------------------- fp32 path (mfgp_f32.hip)
 struct F32Layout {
@@ -1151,18 +1130,57 @@ int mfgp_svgp_workspace_size(mfgp_handle_t h, int n, int m, int l, int p, int d,
     return MFGP_OK;
 }
 
+static SvgpStreams svgp_streams(mfgp_handle_t h) { return SvgpStreams{h->stream, h->side, h->ev_fork, h->ev_join}; }
+
+// The argument checks of the six ELBO entries, before any device work.  go: the gradient outputs of a
+// gradient entry (nullptr: a value entry, whose g_mu / g_var may be NULL and whose noise is a host value).
+static int svgp_check(mfgp_handle_t h, const SvgpProblem& P, const SvgpLik& lik, const SvgpFwdOut& o,
+                      const SvgpGradOut* go) {
+    CHECK_H(h);
+    CHECK_D(P.d);
+    if (P.n < 1 || P.m < 1 || P.l < 1 || P.p < 1 || !P.X || !P.Y || !P.Z || !P.thetas || !P.q_mu || !P.q_sqrt ||
+        !P.ws || !o.out || !P.info)
+        return MFGP_ERR_ARG;
+    if ((go || lik.kind == SvgpLik::MASKED) && !lik.noise_dev) return MFGP_ERR_ARG;
+    if (go && (!o.g_mu || !o.g_var || !go->gZ || !go->gtheta || !go->gq_mu || !go->gq_sqrt || !go->gnoise))
+        return MFGP_ERR_ARG;
+    if (P.qs_packed != 0 && P.qs_packed != 1) return MFGP_ERR_ARG;
+    if (lik.kind == SvgpLik::MASKED && lik.pn != 1 && lik.pn != P.p) return MFGP_ERR_ARG;
+    if (!P.W && P.l != P.p) return MFGP_ERR_ARG;
+    if (go && P.W && !go->gW) return MFGP_ERR_ARG;
+    if (P.ldx < P.d + 1 || P.ldz < P.d + 1 || P.ldy < P.p) return MFGP_ERR_ARG;
+    if (lik.kind == SvgpLik::HET && lik.ldu < P.p) return MFGP_ERR_ARG;
+    // the VE reverse kernels keep a row's state in LDS
+    if (go && lik.kind == SvgpLik::HET && svgp_ve_het_rows(P.p, P.l) == 0) return MFGP_ERR_DIM;
+    if (go && lik.kind == SvgpLik::MASKED && svgp_ve_masked_rows(P.p, P.l) == 0) return MFGP_ERR_DIM;
+    return MFGP_OK;
+}
+
+// noise: the host variance of a value entry; noise_dev: the device variance of a gradient entry
+static SvgpLik svgp_lik_gaussian(double noise, const double* noise_dev, const double* Yunc = nullptr, int ldu = 0) {
+    SvgpLik lik;
+    lik.kind = Yunc ? SvgpLik::HET : SvgpLik::GAUSSIAN;   // Yunc == NULL: the homoscedastic kernels and launches
+    lik.noise = noise; lik.noise_dev = noise_dev;
+    lik.Yunc = Yunc; lik.ldu = ldu;
+    return lik;
+}
+static SvgpLik svgp_lik_masked(const double* noise_dev, int pn) {
+    SvgpLik lik;
+    lik.kind = SvgpLik::MASKED;
+    lik.noise_dev = noise_dev; lik.pn = pn;
+    return lik;
+}
+
 int mfgp_svgp_elbo(mfgp_handle_t h, int n, int m, int l, int p, int d, const double* X, int ldx, const double* Y,
                    int ldy, const double* Z, int ldz, const double* thetas, const double* q_mu,
                    const double* q_sqrt, const double* W, double noise, double scale, double jitter, void* ws,
                    size_t ws_bytes, double* out, double* g_mu, double* g_var, int* info) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (n < 1 || m < 1 || l < 1 || p < 1 || !X || !Y || !Z || !thetas || !q_mu || !q_sqrt || !ws || !out || !info)
-        return MFGP_ERR_ARG;
-    if (!W && l != p) return MFGP_ERR_ARG;
-    svgp_set_side(SvgpSide{h->side, h->ev_fork, h->ev_join});
-    return svgp_elbo_impl(h->stream, h->nb, n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, W, noise,
-                          scale, jitter, ws, ws_bytes, out, g_mu, g_var, info, nullptr);
+    const SvgpProblem P{n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, 0, W, scale, 1.0, jitter,
+                        ws, ws_bytes, info};
+    const SvgpLik lik = svgp_lik_gaussian(noise, nullptr);
+    const SvgpFwdOut o{out, g_mu, g_var};
+    if (const int rc = svgp_check(h, P, lik, o, nullptr)) return rc;
+    return svgp_elbo_impl(h->nb, svgp_streams(h), P, lik, o);
 }
 
 int mfgp_svgp_grad_workspace_size(mfgp_handle_t h, int n, int m, int l, int p, int d, size_t* bytes) {
@@ -1179,33 +1197,25 @@ int mfgp_svgp_elbo_grad(mfgp_handle_t h, int n, int m, int l, int p, int d, cons
                         double scale, double kl_mult, double jitter, void* ws, size_t ws_bytes, double* out, double* g_mu,
                         double* g_var, double* gZ, double* gtheta, double* gq_mu, double* gq_sqrt, double* gW,
                         double* gnoise, int* info) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (n < 1 || m < 1 || l < 1 || p < 1 || !X || !Y || !Z || !thetas || !q_mu || !q_sqrt || !noise || !ws ||
-        !out || !g_mu || !g_var || !gZ || !gtheta || !gq_mu || !gq_sqrt || !gnoise || !info)
-        return MFGP_ERR_ARG;
-    if (W == nullptr && l != p) return MFGP_ERR_ARG;
-    if (W != nullptr && gW == nullptr) return MFGP_ERR_ARG;
-    if (ldx < d + 1 || ldz < d + 1 || ldy < p) return MFGP_ERR_ARG;
-    svgp_set_side(SvgpSide{h->side, h->ev_fork, h->ev_join, h->svgp_qs_packed});
-    return svgp_grad_impl(h->stream, h->nb, n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, W, noise, 0.0,
-                          scale, kl_mult, jitter, ws, ws_bytes, out, g_mu, g_var, gZ, gtheta, gq_mu, gq_sqrt, gW,
-                          gnoise, info);
+    const SvgpProblem P{n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, h ? h->svgp_qs_packed : 0, W, scale, kl_mult, jitter,
+                        ws, ws_bytes, info};
+    const SvgpLik lik = svgp_lik_gaussian(0.0, noise);
+    const SvgpFwdOut o{out, g_mu, g_var};
+    const SvgpGradOut go{gZ, gtheta, gq_mu, gq_sqrt, gW, gnoise};
+    if (const int rc = svgp_check(h, P, lik, o, &go)) return rc;
+    return svgp_grad_impl(h->nb, svgp_streams(h), P, lik, o, go);
 }
 
 int mfgp_svgp_elbo_het(mfgp_handle_t h, int n, int m, int l, int p, int d, const double* X, int ldx, const double* Y,
                        int ldy, const double* Yunc, int ldu, const double* Z, int ldz, const double* thetas,
                        const double* q_mu, const double* q_sqrt, const double* W, double noise, double scale,
                        double jitter, void* ws, size_t ws_bytes, double* out, double* g_mu, double* g_var, int* info) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (n < 1 || m < 1 || l < 1 || p < 1 || !X || !Y || !Z || !thetas || !q_mu || !q_sqrt || !ws || !out || !info)
-        return MFGP_ERR_ARG;
-    if (!W && l != p) return MFGP_ERR_ARG;
-    if (Yunc && (ldu < p || ldy < p)) return MFGP_ERR_ARG;
-    svgp_set_side(SvgpSide{h->side, h->ev_fork, h->ev_join, 0, Yunc, ldu});
-    return svgp_elbo_impl(h->stream, h->nb, n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, W, noise,
-                          scale, jitter, ws, ws_bytes, out, g_mu, g_var, info, nullptr);
+    const SvgpProblem P{n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, 0, W, scale, 1.0, jitter,
+                        ws, ws_bytes, info};
+    const SvgpLik lik = svgp_lik_gaussian(noise, nullptr, Yunc, ldu);
+    const SvgpFwdOut o{out, g_mu, g_var};
+    if (const int rc = svgp_check(h, P, lik, o, nullptr)) return rc;
+    return svgp_elbo_impl(h->nb, svgp_streams(h), P, lik, o);
 }
 
 int mfgp_svgp_elbo_grad_het(mfgp_handle_t h, int n, int m, int l, int p, int d, const double* X, int ldx,
@@ -1214,20 +1224,13 @@ int mfgp_svgp_elbo_grad_het(mfgp_handle_t h, int n, int m, int l, int p, int d, 
                             const double* W, const double* noise, double scale, double kl_mult, double jitter,
                             void* ws, size_t ws_bytes, double* out, double* g_mu, double* g_var, double* gZ,
                             double* gtheta, double* gq_mu, double* gq_sqrt, double* gW, double* gnoise, int* info) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (n < 1 || m < 1 || l < 1 || p < 1 || !X || !Y || !Z || !thetas || !q_mu || !q_sqrt || !noise || !ws ||
-        !out || !g_mu || !g_var || !gZ || !gtheta || !gq_mu || !gq_sqrt || !gnoise || !info)
-        return MFGP_ERR_ARG;
-    if (qs_packed != 0 && qs_packed != 1) return MFGP_ERR_ARG;
-    if (W == nullptr && l != p) return MFGP_ERR_ARG;
-    if (W != nullptr && gW == nullptr) return MFGP_ERR_ARG;
-    if (ldx < d + 1 || ldz < d + 1 || ldy < p || (Yunc && ldu < p)) return MFGP_ERR_ARG;
-    if (Yunc && svgp_ve_het_rows(p, l) == 0) return MFGP_ERR_DIM;
-    svgp_set_side(SvgpSide{h->side, h->ev_fork, h->ev_join, qs_packed, Yunc, ldu});
-    return svgp_grad_impl(h->stream, h->nb, n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, W, noise, 0.0,
-                          scale, kl_mult, jitter, ws, ws_bytes, out, g_mu, g_var, gZ, gtheta, gq_mu, gq_sqrt, gW,
-                          gnoise, info);
+    const SvgpProblem P{n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, qs_packed, W, scale, kl_mult, jitter,
+                        ws, ws_bytes, info};
+    const SvgpLik lik = svgp_lik_gaussian(0.0, noise, Yunc, ldu);
+    const SvgpFwdOut o{out, g_mu, g_var};
+    const SvgpGradOut go{gZ, gtheta, gq_mu, gq_sqrt, gW, gnoise};
+    if (const int rc = svgp_check(h, P, lik, o, &go)) return rc;
+    return svgp_grad_impl(h->nb, svgp_streams(h), P, lik, o, go);
 }
 
 int mfgp_svgp_elbo_masked(mfgp_handle_t h, int n, int m, int l, int p, int d, const double* X, int ldx,
@@ -1235,20 +1238,12 @@ int mfgp_svgp_elbo_masked(mfgp_handle_t h, int n, int m, int l, int p, int d, co
                           const double* q_sqrt, const double* W, const double* noise, int pn, double scale,
                           double jitter, void* ws, size_t ws_bytes, double* out, double* g_mu, double* g_var,
                           int* info) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (n < 1 || m < 1 || l < 1 || p < 1 || !X || !Y || !Z || !thetas || !q_mu || !q_sqrt || !noise || !ws || !out ||
-        !info)
-        return MFGP_ERR_ARG;
-    if (!W && l != p) return MFGP_ERR_ARG;
-    if (pn != 1 && pn != p) return MFGP_ERR_ARG;
-    if (ldy < p) return MFGP_ERR_ARG;
-    SvgpSide sd{h->side, h->ev_fork, h->ev_join};
-    sd.mnoise = noise;
-    sd.pn = pn;
-    svgp_set_side(sd);
-    return svgp_elbo_impl(h->stream, h->nb, n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, W, 0.0, scale,
-                          jitter, ws, ws_bytes, out, g_mu, g_var, info, noise);
+    const SvgpProblem P{n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, 0, W, scale, 1.0, jitter,
+                        ws, ws_bytes, info};
+    const SvgpLik lik = svgp_lik_masked(noise, pn);
+    const SvgpFwdOut o{out, g_mu, g_var};
+    if (const int rc = svgp_check(h, P, lik, o, nullptr)) return rc;
+    return svgp_elbo_impl(h->nb, svgp_streams(h), P, lik, o);
 }
 
 int mfgp_svgp_elbo_grad_masked(mfgp_handle_t h, int n, int m, int l, int p, int d, const double* X, int ldx,
@@ -1257,24 +1252,13 @@ int mfgp_svgp_elbo_grad_masked(mfgp_handle_t h, int n, int m, int l, int p, int 
                                const double* noise, int pn, double scale, double kl_mult, double jitter, void* ws,
                                size_t ws_bytes, double* out, double* g_mu, double* g_var, double* gZ, double* gtheta,
                                double* gq_mu, double* gq_sqrt, double* gW, double* gnoise, int* info) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (n < 1 || m < 1 || l < 1 || p < 1 || !X || !Y || !Z || !thetas || !q_mu || !q_sqrt || !noise || !ws ||
-        !out || !g_mu || !g_var || !gZ || !gtheta || !gq_mu || !gq_sqrt || !gnoise || !info)
-        return MFGP_ERR_ARG;
-    if (qs_packed != 0 && qs_packed != 1) return MFGP_ERR_ARG;
-    if (pn != 1 && pn != p) return MFGP_ERR_ARG;
-    if (W == nullptr && l != p) return MFGP_ERR_ARG;
-    if (W != nullptr && gW == nullptr) return MFGP_ERR_ARG;
-    if (ldx < d + 1 || ldz < d + 1 || ldy < p) return MFGP_ERR_ARG;
-    if (svgp_ve_masked_rows(p, l) == 0) return MFGP_ERR_DIM;
-    SvgpSide sd{h->side, h->ev_fork, h->ev_join, qs_packed};
-    sd.mnoise = noise;
-    sd.pn = pn;
-    svgp_set_side(sd);
-    return svgp_grad_impl(h->stream, h->nb, n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, W, noise, 0.0,
-                          scale, kl_mult, jitter, ws, ws_bytes, out, g_mu, g_var, gZ, gtheta, gq_mu, gq_sqrt, gW,
-                          gnoise, info);
+    const SvgpProblem P{n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, qs_packed, W, scale, kl_mult, jitter,
+                        ws, ws_bytes, info};
+    const SvgpLik lik = svgp_lik_masked(noise, pn);
+    const SvgpFwdOut o{out, g_mu, g_var};
+    const SvgpGradOut go{gZ, gtheta, gq_mu, gq_sqrt, gW, gnoise};
+    if (const int rc = svgp_check(h, P, lik, o, &go)) return rc;
+    return svgp_grad_impl(h->nb, svgp_streams(h), P, lik, o, go);
 }
 
 int mfgp_set_svgp_qs_packed(mfgp_handle_t h, int packed) {
@@ -1318,9 +1302,9 @@ int mfgp_svgp_predict(mfgp_handle_t h, int nstar, int m, int l, int p, int d, co
         !g_var || !f_mu || !f_var || !info)
         return MFGP_ERR_ARG;
     if (!W && l != p) return MFGP_ERR_ARG;
-    svgp_set_side(SvgpSide{h->side, h->ev_fork, h->ev_join});
-    return svgp_predict_impl(h->stream, h->nb, nstar, m, l, p, d, Xs, ldxs, Z, ldz, thetas, q_mu, q_sqrt, W, jitter,
-                             ws, ws_bytes, g_mu, g_var, f_mu, f_var, info);
+    const SvgpProblem P{nstar, m, l, p, d, Xs, ldxs, nullptr, 0, Z, ldz, thetas, q_mu, q_sqrt, 0, W, 1.0, 1.0, jitter,
+                        ws, ws_bytes, info};
+    return svgp_predict_impl(h->nb, svgp_streams(h), P, SvgpFwdOut{nullptr, g_mu, g_var, f_mu, f_var});
 }
 
 int mfgp_svgp_predict_cov_workspace_size(mfgp_handle_t h, int nstar, int m, int l, int p, int d, size_t* bytes) {
@@ -1341,9 +1325,10 @@ int mfgp_svgp_predict_cov(mfgp_handle_t h, int mode, int nstar, int m, int l, in
         !ws || !g_mu || !g_var || !f_mu || !f_var || !f_cov || !info)
         return MFGP_ERR_ARG;
     if (!W && l != p) return MFGP_ERR_ARG;
-    svgp_set_side(SvgpSide{h->side, h->ev_fork, h->ev_join});
-    const int rc = svgp_predict_cov_impl(h->stream, h->nb, mode, nstar, m, l, p, d, Xs, ldxs, Z, ldz, thetas, q_mu,
-                                         q_sqrt, W, jitter, ws, ws_bytes, g_mu, g_var, f_mu, f_var, f_cov, info);
+    const SvgpProblem P{nstar, m, l, p, d, Xs, ldxs, nullptr, 0, Z, ldz, thetas, q_mu, q_sqrt, 0, W, 1.0, 1.0, jitter,
+                        ws, ws_bytes, info};
+    const int rc = svgp_predict_cov_impl(h->nb, svgp_streams(h), P, SvgpFwdOut{nullptr, g_mu, g_var, f_mu, f_var},
+                                         SvgpCovOut{mode, f_cov});
     return rc == -2 ? MFGP_ERR_WORKSPACE : (rc ? MFGP_ERR_LAUNCH : MFGP_OK);
 }
 

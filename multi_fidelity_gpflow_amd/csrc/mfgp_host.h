@@ -38,10 +38,6 @@ struct mfgp_handle_s {
 #define CHECK_D(d) \
     if ((d) < 1 || (d) > MFGP_MAX_D) return MFGP_ERR_DIM
 
-// The one tile-size dispatch: fn<64>(args) or fn<32>(args), the argument list written once.
-#define TILE_CALL(nb, fn, ...) \
-    ((nb) == 64 ? fn<64>(__VA_ARGS__) : fn<32>(__VA_ARGS__))
-
 namespace mfgp {
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
@@ -49,19 +45,6 @@ static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 constexpr double GRAPH_JITTER = 1e-6;   // graph.py:96: K_full += 1e-6 I
 
 static inline hipError_t last() { return hipGetLastError(); }
-
-struct Carve {
-    char* base;
-    size_t off = 0;
-    explicit Carve(void* b) : base((char*)b) {}
-    template <class T>
-    T* take(size_t count) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += count * sizeof(T);
-        return p;
-    }
-};
 
 struct GprLayout {
     int nb, npad, T, ppad, Tp, G, gstride, ng;

@@ -3,7 +3,25 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+// The one tile-size dispatch: fn<64>(args) or fn<32>(args), the argument list written once.
+#define TILE_CALL(nb, fn, ...) \
+    ((nb) == 64 ? fn<64>(__VA_ARGS__) : fn<32>(__VA_ARGS__))
+
 namespace mfgp {
+
+// Workspace carving: every block starts on a 256-byte boundary; base == nullptr only counts.
+struct Carve {
+    char* base;
+    size_t off = 0;
+    explicit Carve(void* b) : base((char*)b) {}
+    template <class T>
+    T* take(size_t count) {
+        off = (off + 255) & ~(size_t)255;
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += count * sizeof(T);
+        return p;
+    }
+};
 
 struct GramArgs {
     const double* X1; long ldx1; long sx1; int n1;
@@ -271,12 +289,6 @@ struct DesignArgs {
 template <int NB> void launch_design_score(const DesignArgs& a, hipStream_t s);
 void launch_design_row(const DesignArgs& a, hipStream_t s);
 
-// tril(q_sqrt) zero padded / C = Lq^T Linv of the SVGP K_uu pipeline, into caller buffers (mfgp_svgp.hip)
-int svgp_posterior_factor(hipStream_t s, int nb, int m, int l, int d, const double* Z, int ldz, const double* thetas,
-                          const double* q_sqrt, double jitter, void* ws, size_t ws_bytes, double* Li, double* C,
-                          int* info);
-size_t svgp_posterior_factor_bytes(int nb, int m, int l);
-
 // Batched fp64 MFMA GEMM (k_bgemm, mfgp_svgp_grad.hip), NB x NB output tiles:
 // D = (alpha * op(A) diag(s) op(B) + beta * Cin) [* diag(colscale)] + x y^T   (tril: zero j > i)
 struct BgemmArgs {
@@ -305,33 +317,100 @@ struct BgemmArgs {
 };
 void launch_bgemm(int nb, hipStream_t st, int ta, int tb, const BgemmArgs& a, int batch);
 
-// The handle's side stream and fork / join events for the SVGP calls' independent branches (the
-// K_uu factorization beside the K_uf Gram; the reverse pass's dE/dm, dE/dLq and K_diag terms beside
-// the gA -> Sigma_bar / K_bar -> kernel-derivative chain).  Set by the C-ABI entry points for the
-// calling thread; side == nullptr: everything on the caller's stream.
-// per-call SVGP settings of the calling thread (svgp_set_side, from the handle at each entry):
-// its side stream and fork / join events; qs_packed: q_sqrt / gq_sqrt of the gradient entry as packed
-// lower triangles [L][M(M+1)/2] (mfgp_set_svgp_qs_packed, or mfgp_svgp_elbo_grad_het's argument);
-// Yunc / ldu: the per-observation uncertainties [n][ldu] of the heteroscedastic entry points
-// (nullptr: the homoscedastic Gaussian likelihood, today's kernels and launch sequence);
-// mnoise / pn: the device noise vector of the MaskedGaussian entry points, pn = 1 or p entries
-// (pn == 0: not masked; NaN targets then propagate as they always did)
-struct SvgpSide {
-    hipStream_t side; hipEvent_t fork, join; int qs_packed = 0;
-    const double* Yunc = nullptr; int ldu = 0;
-    const double* mnoise = nullptr; int pn = 0;
+// ---------------------------------------------------------------- SVGP host layer (mfgp_svgp.hip, mfgp_svgp_grad.hip)
+// One SVGP call is described by plain structs that the C-ABI entry fills once and every driver takes
+// by const reference: a driver's signature names everything it reads, and nothing else does.
+
+// The caller's stream, and the handle's side stream with its fork / join events for the calls'
+// independent branches (the K_uu factorization beside the K_uf Gram; the reverse pass's dE/dm, dE/dLq
+// and K_diag terms beside the gA -> Sigma_bar / K_bar -> kernel-derivative chain).  Without a side
+// stream everything stays on main.
+struct SvgpStreams {
+    hipStream_t main, side;
+    hipEvent_t ev_fork, ev_join;
+    bool has_side() const { return side && ev_fork && ev_join; }
+    // fork the side stream off main; returns the stream to launch the branch on
+    hipStream_t fork() const {
+        if (!has_side()) return main;
+        (void)hipEventRecord(ev_fork, main);
+        (void)hipStreamWaitEvent(side, ev_fork, 0);
+        return side;
+    }
+    void join() const {
+        if (!has_side()) return;
+        (void)hipEventRecord(ev_join, side);
+        (void)hipStreamWaitEvent(main, ev_join, 0);
+    }
 };
-void svgp_set_side(const SvgpSide& sd);
-const SvgpSide& svgp_side();
+
+// The likelihood of an ELBO call.  The kernels take the Gaussian / heteroscedastic variance as the
+// pair (noise, noise_dev), noise_dev winning when set: the value entries give the host value alone,
+// the gradient entries the device scalar alone (noise stays 0).
+struct SvgpLik {
+    enum Kind {
+        GAUSSIAN,   // one variance for every observation
+        HET,        // variance + Yunc^2 per observation (Yunc [n][ldu])
+        MASKED      // NaN targets are missing; noise_dev holds pn = 1 or p variances
+    } kind = GAUSSIAN;
+    double noise = 0.0;
+    const double* noise_dev = nullptr;
+    const double* Yunc = nullptr; int ldu = 0;
+    int pn = 0;
+};
+
+// What every SVGP driver reads.  The predict drivers leave Y unset (X holds the test inputs, n their count).
+struct SvgpProblem {
+    int n, m, l, p, d;
+    const double* X; int ldx;
+    const double* Y; int ldy;
+    const double* Z; int ldz;
+    const double* thetas; const double* q_mu; const double* q_sqrt;
+    int qs_packed;            // q_sqrt (and gq_sqrt) as packed lower triangles [l][m(m+1)/2]
+    const double* W;          // mixing [p][l]; nullptr: identity (l == p)
+    double scale, kl_mult, jitter;
+    void* ws; size_t ws_bytes;
+    int* info;
+};
+
+// What the forward writes: out = [elbo, KL, VE] and the latent moments; with f_mu / f_var set it is a
+// predict (mixed moments only, no likelihood); Aout / Bout keep A = Li Kuf and B = Lq^T A
+// ([l][Mpad][Npad] each) for the gradient pass.
+struct SvgpFwdOut {
+    double *out, *g_mu, *g_var;
+    double *f_mu = nullptr, *f_var = nullptr;
+    double *Aout = nullptr, *Bout = nullptr;
+};
+struct SvgpGradOut { double *gZ, *gtheta, *gq_mu, *gq_sqrt, *gW, *gnoise; };
+struct SvgpCovOut { int mode; double* f_cov; };   // mode: 1 full_cov, 2 full_output_cov, 3 both
+
+struct SvgpLayout {
+    int nb, Tm, mpad, Tn, npad, G;
+    double *Kuu, *R, *Xo, *Dd, *ldiag, *Lq, *C, *Kuf, *pa, *pb, *pm, *ve_part, *kl_part;
+    size_t bytes;
+};
+SvgpLayout svgp_layout(int nb, int n, int m, int l, int p, int d, void* ws);
+size_t svgp_workspace_bytes(int nb, int n, int m, int l, int p, int d);
+size_t svgp_grad_workspace_bytes(int nb, int n, int m, int l, int p, int d);
+size_t svgp_predict_cov_workspace_bytes(int nb, int ns, int m, int l, int p, int d);
+
+// Return codes of the drivers: 0, -2 workspace too small, -3 launch error, -4 the VE reverse kernel's
+// row state does not fit (svgp_ve_*_rows == 0).
+int svgp_elbo_impl(int nb, const SvgpStreams& st, const SvgpProblem& P, const SvgpLik& lik, const SvgpFwdOut& o);
+int svgp_predict_impl(int nb, const SvgpStreams& st, const SvgpProblem& P, const SvgpFwdOut& o);
+int svgp_grad_impl(int nb, const SvgpStreams& st, const SvgpProblem& P, const SvgpLik& lik, const SvgpFwdOut& o,
+                   const SvgpGradOut& go);
+int svgp_predict_cov_impl(int nb, const SvgpStreams& st, const SvgpProblem& P, const SvgpFwdOut& o,
+                          const SvgpCovOut& co);
+// Lm^{-1} zero padded / C = Lq^T Lm^{-1} of the SVGP K_uu pipeline into the caller's cache blocks
+// ([l][Mpad][Mpad] each), on s alone; reads m, l, d, Z, thetas, q_sqrt, jitter, ws and info of P
+int svgp_posterior_factor(int nb, hipStream_t s, const SvgpProblem& P, double* Li, double* C);
+size_t svgp_posterior_factor_bytes(int nb, int m, int l);
+
 // rows a workgroup of the heteroscedastic VE reverse kernel takes (k_ve_bwd_het) for p outputs and
 // l latents; 0: the row state of one row does not fit its LDS budget (MFGP_ERR_DIM)
 int svgp_ve_het_rows(int p, int l);
 // the same for the masked VE reverse kernel (k_ve_bwd_masked), whose row state has a third [rb][p|1] tile
 int svgp_ve_masked_rows(int p, int l);
-
-// fork the side stream off s (nothing without a side stream); returns the stream to launch on
-hipStream_t svgp_fork(hipStream_t s);
-void svgp_join(hipStream_t s);
 
 constexpr int MAXD_HOST = 32;
 

@@ -297,8 +297,11 @@ static int svgp_posterior_build_impl(mfgp_handle_t h, int m, int l, int p, int d
     const SvgpCache c = svgp_cache_layout(h->nb, m, l, p, d, cache);
     if (cache_bytes < c.bytes || ws_bytes < svgp_posterior_factor_bytes(h->nb, m, l)) return MFGP_ERR_WORKSPACE;
     hipStream_t s = h->stream;
-    const int rc = svgp_posterior_factor(s, h->nb, m, l, d, Z, ldz, thetas, q_sqrt, jitter, ws, ws_bytes, c.Li, c.C,
-                                         info);
+    SvgpProblem P{};
+    P.m = m; P.l = l; P.p = p; P.d = d;
+    P.Z = Z; P.ldz = ldz; P.thetas = thetas; P.q_mu = q_mu; P.q_sqrt = q_sqrt; P.W = W;
+    P.jitter = jitter; P.ws = ws; P.ws_bytes = ws_bytes; P.info = info;
+    const int rc = svgp_posterior_factor(h->nb, s, P, c.Li, c.C);
     if (rc) return rc == -2 ? MFGP_ERR_WORKSPACE : MFGP_ERR_LAUNCH;
     copy_block(s, Z, ldz, c.Z, d + 1, m, d + 1);
     copy_block(s, thetas, c.G, c.thetas, c.G, l, c.G);

@@ -19,29 +19,7 @@ namespace mfgp {
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-static thread_local SvgpSide t_side{nullptr, nullptr, nullptr};
-void svgp_set_side(const SvgpSide& sd) { t_side = sd; }
-const SvgpSide& svgp_side() { return t_side; }
-hipStream_t svgp_fork(hipStream_t s) {
-    if (!t_side.side || !t_side.fork || !t_side.join) return s;
-    (void)hipEventRecord(t_side.fork, s);
-    (void)hipStreamWaitEvent(t_side.side, t_side.fork, 0);
-    return t_side.side;
-}
-void svgp_join(hipStream_t s) {
-    if (!t_side.side || !t_side.fork || !t_side.join) return;
-    (void)hipEventRecord(t_side.join, t_side.side);
-    (void)hipStreamWaitEvent(s, t_side.join, 0);
-}
-
-
-struct SvgpLayout {
-    int nb, Tm, mpad, Tn, npad, G;
-    double *Kuu, *R, *Xo, *Dd, *ldiag, *Lq, *C, *Kuf, *pa, *pb, *pm, *ve_part, *kl_part;
-    size_t bytes;
-};
-
-static SvgpLayout svgp_layout(int nb, int n, int m, int l, int p, int d, void* ws) {
+SvgpLayout svgp_layout(int nb, int n, int m, int l, int p, int d, void* ws) {
     SvgpLayout S;
     S.nb = nb;
     S.Tm = cdiv(m, nb);
@@ -50,45 +28,26 @@ static SvgpLayout svgp_layout(int nb, int n, int m, int l, int p, int d, void* w
     S.npad = S.Tn * nb;
     S.G = theta_size(d);
     const size_t mm = (size_t)S.mpad * S.mpad;
-    size_t off = 0;
-    char* base = (char*)ws;
-    auto take = [&](size_t count) {
-        off = (off + 255) & ~(size_t)255;
-        double* ptr = base ? reinterpret_cast<double*>(base + off) : nullptr;
-        off += count * sizeof(double);
-        return ptr;
-    };
-    S.Kuu = take(mm * l);
-    S.R = take(mm * l);
-    S.Xo = take(mm * l);
-    S.Dd = take((size_t)S.Tm * nb * nb * l);
-    S.ldiag = take((size_t)S.mpad * l);
-    S.Lq = take(mm * l);
-    S.C = take(mm * l);
-    S.Kuf = take((size_t)S.mpad * S.npad * l);
-    S.pa = take((size_t)l * S.Tm * S.npad);
-    S.pb = take((size_t)l * S.Tm * S.npad);
-    S.pm = take((size_t)l * S.Tm * S.npad);
-    S.ve_part = take(1024);
-    S.kl_part = take((size_t)l * 8 + 8);   // KL_SLICES partials per latent
-    S.bytes = off + 256;
+    Carve c(ws);
+    S.Kuu = c.take<double>(mm * l);
+    S.R = c.take<double>(mm * l);
+    S.Xo = c.take<double>(mm * l);
+    S.Dd = c.take<double>((size_t)S.Tm * nb * nb * l);
+    S.ldiag = c.take<double>((size_t)S.mpad * l);
+    S.Lq = c.take<double>(mm * l);
+    S.C = c.take<double>(mm * l);
+    S.Kuf = c.take<double>((size_t)S.mpad * S.npad * l);
+    S.pa = c.take<double>((size_t)l * S.Tm * S.npad);
+    S.pb = c.take<double>((size_t)l * S.Tm * S.npad);
+    S.pm = c.take<double>((size_t)l * S.Tm * S.npad);
+    S.ve_part = c.take<double>(1024);
+    S.kl_part = c.take<double>((size_t)l * 8 + 8);   // KL_SLICES partials per latent
+    S.bytes = c.off + 256;
     return S;
 }
 
 size_t svgp_workspace_bytes(int nb, int n, int m, int l, int p, int d) {
     return svgp_layout(nb, n, m, l, p, d, nullptr).bytes;
-}
-
-// forward intermediates for the gradient pass (mfgp_svgp_grad.hip)
-void svgp_forward_buffers(int nb, int n, int m, int l, int p, int d, void* ws, double** Xo, double** C, double** Kuf,
-                          double** Lq, int* mpad, int* npad) {
-    const SvgpLayout S = svgp_layout(nb, n, m, l, p, d, ws);
-    *Xo = S.Xo;
-    *C = S.C;
-    *Kuf = S.Kuf;
-    *Lq = S.Lq;
-    *mpad = S.mpad;
-    *npad = S.npad;
 }
 
 // Zeros in the strictly-upper tiles of L^{-1} (the step sequence writes only tiles (i, c <= i)):
@@ -590,68 +549,73 @@ __global__ __launch_bounds__(NTHREADS) void k_svgp_final(const double* ve_part, 
     out[2] = ve;
 }
 
+// The K_uu head the forward and the cached-posterior factor build share: K_uu (+ jitter, RHS = I) of
+// every latent by one Gram launch and the first diagonal factor (the first writer of info), both on s;
+// returns the argument block of the remaining steps, which the caller launches on the stream it
+// chooses (launch_chol_steps).  S: SvgpLayout or SvgpFactorLayout; Li: where [L^{-1}] goes.
+template <int NB, class Layout>
+static CholArgs svgp_kuu_head(hipStream_t s, const SvgpProblem& P, const Layout& S, double* Li) {
+    const long mm = (long)S.mpad * S.mpad;
+    GramArgs g{};
+    g.X1 = P.Z; g.ldx1 = P.ldz; g.sx1 = 0; g.n1 = P.m;
+    g.X2 = P.Z; g.ldx2 = P.ldz; g.sx2 = 0; g.n2 = P.m;
+    g.theta = P.thetas; g.stheta = theta_size(P.d); g.D = P.d; g.rbf_only = 0;
+    g.out = S.Kuu; g.ldo = S.mpad; g.so = mm;
+    g.padded = 1; g.npad = S.mpad; g.tiles_c = S.Tm; g.add_noise = 0; g.diag_add = P.jitter;
+    // NB = 32: R = I stays implicit in the batched steps (CholArgs::r_implicit); the Gram
+    // wrote 52 MB of identity at Goku on the chain's critical path
+    g.R = NB == 32 ? nullptr : S.R; g.ldr = S.mpad; g.sR = mm;
+    // the dense-layout Gram (64 x 64 entries a workgroup, both triangles): the lean tile
+    // launch took 56-66 us for 64 latents of 300 x 300 on the chain's critical path
+    launch_gram_dense(g, P.l, S.mpad, S.mpad, s);
+    launch_first_factor<NB>(S.Kuu, S.mpad, mm, S.Dd, (long)S.Tm * NB * NB, S.ldiag, S.mpad, P.info, P.l, s);
+    CholArgs c{};
+    c.A = S.Kuu; c.lda = S.mpad; c.sA = mm;
+    c.R = S.R; c.ldr = S.mpad; c.sR = mm;
+    c.Xo = Li; c.ldx = S.mpad; c.sX = mm;
+    c.Dd = S.Dd; c.sD = (long)S.Tm * NB * NB; c.ldiag = S.ldiag; c.sL = S.mpad; c.info = P.info;
+    c.T = S.Tm; c.Tp = 0; c.k = 0;
+    c.r_implicit = NB == 32 ? 1 : 0;   // k_chol_fused (NB = 32) forms R's identity and zeros itself
+    return c;
+}
+
 template <int NB>
-static int svgp_run(hipStream_t s, int n, int m, int L, int p, int d, const double* X, int ldx, const double* Y,
-                    int ldy, const double* Z, int ldz, const double* thetas, const double* q_mu,
-                    const double* q_sqrt, const double* W, double noise, double scale, double jitter, void* ws,
-                    size_t ws_bytes, double* out, double* g_mu, double* g_var, int* info, double* f_mu = nullptr,
-                    double* f_var = nullptr, const double* noise_dev = nullptr, double* Aout = nullptr,
-                    double* Bout = nullptr) {
-    const SvgpLayout S = svgp_layout(NB, n, m, L, p, d, ws);
-    if (ws_bytes < S.bytes) return -2;
+static int svgp_run(const SvgpStreams& st, const SvgpProblem& P, const SvgpLik& lik, const SvgpFwdOut& o) {
+    const int n = P.n, m = P.m, L = P.l, p = P.p;
+    const hipStream_t s = st.main;
+    const SvgpLayout S = svgp_layout(NB, n, m, L, p, P.d, P.ws);
+    if (P.ws_bytes < S.bytes) return -2;
     const long mm = (long)S.mpad * S.mpad;
     // The gradient pass keeps A and B (Aout / Bout) anyway, so there they come from two batched
     // GEMMs, A = Li Kuf (Li lower) and B = Lq^T A (Lq^T upper): 2 x 8.5 GF at Goku (L = 64)
     // against the fused conditional's 8.5 + 17 (B = C Kuf with the full C = Lq^T Li, which it
     // needs to form A and B in one tile loop without keeping A), and no C.  The column moments
     // come out of the GEMMs' epilogues in the fused kernel's partial layout and order.
-    const bool two_gemm = NB == 32 && Aout != nullptr;
-    // K_uu (+ jitter, RHS = I) by one Gram launch and the first diagonal factor of every latent
-    // (the first writer of info) on the caller's stream, alone; then the rest of the K_uu pipeline
+    const bool two_gemm = NB == 32 && o.Aout != nullptr;
+    // The K_uu head on the caller's stream, alone; then the rest of the K_uu pipeline
     // (latency-bound: ~20 launches of small grids, the forward's critical path) on the side stream,
     // and the K_uf Gram, tril(q_sqrt), the zeros above Li's tiles (the step sequence never writes
     // there) and the KL on the caller's beside it.  (Forked before the first factor, the K_uf
     // Gram's 24k workgroups held the CUs: the 64 one-workgroup factors took 64 us instead of ~5.)
-    hipStream_t sk;
-    {
-        GramArgs g{};
-        g.X1 = Z; g.ldx1 = ldz; g.sx1 = 0; g.n1 = m;
-        g.X2 = Z; g.ldx2 = ldz; g.sx2 = 0; g.n2 = m;
-        g.theta = thetas; g.stheta = S.G; g.D = d; g.rbf_only = 0;
-        g.out = S.Kuu; g.ldo = S.mpad; g.so = mm;
-        g.padded = 1; g.npad = S.mpad; g.tiles_c = S.Tm; g.add_noise = 0; g.diag_add = jitter;
-        // NB = 32: R = I stays implicit in the batched steps (CholArgs::r_implicit); the Gram
-        // wrote 52 MB of identity at Goku on the chain's critical path
-        g.R = NB == 32 ? nullptr : S.R; g.ldr = S.mpad; g.sR = mm;
-        // the dense-layout Gram (64 x 64 entries a workgroup, both triangles): the lean tile
-        // launch took 56-66 us for 64 latents of 300 x 300 on the chain's critical path
-        launch_gram_dense(g, L, S.mpad, S.mpad, s);
-        launch_first_factor<NB>(S.Kuu, S.mpad, mm, S.Dd, (long)S.Tm * NB * NB, S.ldiag, S.mpad, info, L, s);
-        sk = svgp_fork(s);
-        CholArgs c{};
-        c.A = S.Kuu; c.lda = S.mpad; c.sA = mm;
-        c.R = S.R; c.ldr = S.mpad; c.sR = mm;
-        c.Xo = S.Xo; c.ldx = S.mpad; c.sX = mm;
-        c.Dd = S.Dd; c.sD = (long)S.Tm * NB * NB; c.ldiag = S.ldiag; c.sL = S.mpad; c.info = info;
-        c.T = S.Tm; c.Tp = 0; c.k = 0;
-        c.r_implicit = NB == 32 ? 1 : 0;   // k_chol_fused (NB = 32) forms R's identity and zeros itself
-        launch_chol_steps<NB>(c, L, sk);
-    }
+    const CholArgs c = svgp_kuu_head<NB>(s, P, S, S.Xo);
+    launch_chol_steps<NB>(c, L, st.fork());
     hipLaunchKernelGGL(k_zero_upper_tiles, dim3(cdiv(S.mpad, ZU_ROWS), 1, L), dim3(256), 0, s, S.Xo, NB, S.mpad, mm);
     // Kuf_l = K_l(Z, X), zero padded to Mpad x Npad
     {
         GramArgs g{};
-        g.X1 = Z; g.ldx1 = ldz; g.sx1 = 0; g.n1 = m;
-        g.X2 = X; g.ldx2 = ldx; g.sx2 = 0; g.n2 = n;
-        g.theta = thetas; g.stheta = S.G; g.D = d; g.rbf_only = 0;
+        g.X1 = P.Z; g.ldx1 = P.ldz; g.sx1 = 0; g.n1 = m;
+        g.X2 = P.X; g.ldx2 = P.ldx; g.sx2 = 0; g.n2 = n;
+        g.theta = P.thetas; g.stheta = S.G; g.D = P.d; g.rbf_only = 0;
         g.out = S.Kuf; g.ldo = S.npad; g.so = (long)S.mpad * S.npad;
         g.padded = 0; g.tiles_c = S.Tn; g.diag_add = 0.0;
         launch_gram_dense(g, L, S.mpad, S.npad, s);   // zero padding written by the kernel
     }
-    const int qp = t_side.qs_packed;
-    hipLaunchKernelGGL(k_lq_pad, dim3(cdiv(S.mpad, ZU_ROWS), 1, L), dim3(256), 0, s, q_sqrt, m, S.mpad, S.Lq, qp);
-    if (!f_mu) hipLaunchKernelGGL(k_svgp_kl, dim3(KL_SLICES, L), dim3(NTHREADS), 0, s, q_mu, q_sqrt, m, L, S.kl_part, qp);
-    svgp_join(s);
+    hipLaunchKernelGGL(k_lq_pad, dim3(cdiv(S.mpad, ZU_ROWS), 1, L), dim3(256), 0, s, P.q_sqrt, m, S.mpad, S.Lq,
+                       P.qs_packed);
+    if (!o.f_mu)
+        hipLaunchKernelGGL(k_svgp_kl, dim3(KL_SLICES, L), dim3(NTHREADS), 0, s, P.q_mu, P.q_sqrt, m, L, S.kl_part,
+                           P.qs_packed);
+    st.join();
     if (!two_gemm)   // C = Lq^T Li (the fused conditional's B = C Kuf), after Lq and Li
         hipLaunchKernelGGL(k_lqt_linv<NB>, dim3(S.Tm * S.Tm, 1, L), dim3(NTHREADS), 2 * sizeof(double) * NB * (NB + 2),
                            s, S.Lq, S.Xo, S.C, S.Tm);
@@ -661,16 +625,16 @@ static int svgp_run(hipStream_t s, int n, int m, int L, int p, int d, const doub
         ga.amask = 1;   // Li lower
         ga.A = S.Xo; ga.lda = S.mpad; ga.sA = mm;
         ga.B = S.Kuf; ga.ldb = S.npad; ga.sB = mn;
-        ga.D = Aout; ga.ldd = S.npad; ga.sD = mn;
+        ga.D = o.Aout; ga.ldd = S.npad; ga.sD = mn;
         ga.alpha = 1.0;
         ga.Mt = S.Tm; ga.Nt = S.Tn; ga.Kt = S.Tm;
-        ga.csq = S.pa; ga.csq2 = S.pm; ga.ldcs = S.npad; ga.qv = q_mu; ga.qs = L; ga.qn = m;
+        ga.csq = S.pa; ga.csq2 = S.pm; ga.ldcs = S.npad; ga.qv = P.q_mu; ga.qs = L; ga.qn = m;
         launch_bgemm(NB, s, 0, 0, ga, L);
         BgemmArgs gb{};
         gb.amask = 2;   // Lq^T upper
         gb.A = S.Lq; gb.lda = S.mpad; gb.sA = mm;
-        gb.B = Aout; gb.ldb = S.npad; gb.sB = mn;
-        gb.D = Bout; gb.ldd = S.npad; gb.sD = mn;
+        gb.B = o.Aout; gb.ldb = S.npad; gb.sB = mn;
+        gb.D = o.Bout; gb.ldd = S.npad; gb.sD = mn;
         gb.alpha = 1.0;
         gb.Mt = S.Tm; gb.Nt = S.Tn; gb.Kt = S.Tm;
         gb.csq = S.pb; gb.ldcs = S.npad;
@@ -683,68 +647,41 @@ static int svgp_run(hipStream_t s, int n, int m, int L, int p, int d, const doub
             attr = true;
         }
         hipLaunchKernelGGL(k_svgp_cond2, dim3(((S.Tm + 1) >> 1) * ((S.Tn + 1) >> 1), 1, L), dim3(NTHREADS),
-                           svgp_cond2_smem(), s, S.Xo, S.C, S.Kuf, q_mu, L, m, S.Tm, S.npad, S.pa, S.pb, S.pm, Aout,
-                           Bout);
+                           svgp_cond2_smem(), s, S.Xo, S.C, S.Kuf, P.q_mu, L, m, S.Tm, S.npad, S.pa, S.pb, S.pm,
+                           o.Aout, o.Bout);
     } else {
         hipLaunchKernelGGL(k_svgp_cond<NB>, dim3(S.Tm * S.Tn, 1, L), dim3(NTHREADS),
-                           sizeof(double) * (3 * NB * (NB + 2) + 12 * NB), s, S.Xo, S.C, S.Kuf, q_mu, L, m, S.Tm,
-                           S.npad, S.pa, S.pb, S.pm, Aout, Bout);
+                           sizeof(double) * (3 * NB * (NB + 2) + 12 * NB), s, S.Xo, S.C, S.Kuf, P.q_mu, L, m, S.Tm,
+                           S.npad, S.pa, S.pb, S.pm, o.Aout, o.Bout);
     }
-    hipLaunchKernelGGL(k_svgp_moments, dim3(cdiv(n, 256), 1, L), dim3(256), 0, s, S.pa, S.pb, S.pm, X, (long)ldx,
-                       thetas, S.G, d, n, S.npad, S.Tm, g_mu, g_var);
-    if (f_mu) {   // predict: mixed moments only
-        hipLaunchKernelGGL(k_svgp_mix, dim3(std::min(cdiv(n * p, 256), 2048)), dim3(256), 0, s, g_mu, g_var, W, n, p, L,
-                           f_mu, f_var);
+    hipLaunchKernelGGL(k_svgp_moments, dim3(cdiv(n, 256), 1, L), dim3(256), 0, s, S.pa, S.pb, S.pm, P.X,
+                       (long)P.ldx, P.thetas, S.G, P.d, n, S.npad, S.Tm, o.g_mu, o.g_var);
+    if (o.f_mu) {   // predict: mixed moments only
+        hipLaunchKernelGGL(k_svgp_mix, dim3(std::min(cdiv(n * p, 256), 2048)), dim3(256), 0, s, o.g_mu, o.g_var, P.W, n,
+                           p, L, o.f_mu, o.f_var);
         return hipGetLastError() == hipSuccess ? 0 : -3;
     }
     const int nve = 512;
-    if (t_side.pn)
-        hipLaunchKernelGGL(k_svgp_ve_masked, dim3(nve), dim3(NTHREADS), 0, s, g_mu, g_var, W, Y, (long)ldy, n, p, L,
-                           t_side.mnoise, t_side.pn, S.ve_part);
-    else if (t_side.Yunc)
-        hipLaunchKernelGGL(k_svgp_ve_het, dim3(nve), dim3(NTHREADS), 0, s, g_mu, g_var, W, Y, (long)ldy, t_side.Yunc,
-                           (long)t_side.ldu, n, p, L, noise, noise_dev, S.ve_part);
+    if (lik.kind == SvgpLik::MASKED)
+        hipLaunchKernelGGL(k_svgp_ve_masked, dim3(nve), dim3(NTHREADS), 0, s, o.g_mu, o.g_var, P.W, P.Y, (long)P.ldy, n,
+                           p, L, lik.noise_dev, lik.pn, S.ve_part);
+    else if (lik.kind == SvgpLik::HET)
+        hipLaunchKernelGGL(k_svgp_ve_het, dim3(nve), dim3(NTHREADS), 0, s, o.g_mu, o.g_var, P.W, P.Y, (long)P.ldy,
+                           lik.Yunc, (long)lik.ldu, n, p, L, lik.noise, lik.noise_dev, S.ve_part);
     else
-        hipLaunchKernelGGL(k_svgp_ve, dim3(nve), dim3(NTHREADS), 0, s, g_mu, g_var, W, Y, (long)ldy, n, p, L, noise,
-                           noise_dev, S.ve_part);
+        hipLaunchKernelGGL(k_svgp_ve, dim3(nve), dim3(NTHREADS), 0, s, o.g_mu, o.g_var, P.W, P.Y, (long)P.ldy, n, p, L,
+                           lik.noise, lik.noise_dev, S.ve_part);
     hipLaunchKernelGGL(k_svgp_final, dim3(1), dim3(NTHREADS), 0, s, S.ve_part, nve, S.kl_part, L * KL_SLICES, m, L,
-                       scale, info, out);
+                       P.scale, P.info, o.out);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-int svgp_elbo_impl(hipStream_t s, int nb, int n, int m, int l, int p, int d, const double* X, int ldx,
-                   const double* Y, int ldy, const double* Z, int ldz, const double* thetas, const double* q_mu,
-                   const double* q_sqrt, const double* W, double noise, double scale, double jitter, void* ws,
-                   size_t ws_bytes, double* out, double* g_mu, double* g_var, int* info, const double* noise_dev) {
-    if (nb == 64)
-        return svgp_run<64>(s, n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, W, noise, scale, jitter,
-                            ws, ws_bytes, out, g_mu, g_var, info, nullptr, nullptr, noise_dev);
-    return svgp_run<32>(s, n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, W, noise, scale, jitter, ws,
-                        ws_bytes, out, g_mu, g_var, info, nullptr, nullptr, noise_dev);
+int svgp_elbo_impl(int nb, const SvgpStreams& st, const SvgpProblem& P, const SvgpLik& lik, const SvgpFwdOut& o) {
+    return TILE_CALL(nb, svgp_run, st, P, lik, o);
 }
 
-// the ELBO forward that also writes A = Li Kuf and B = C Kuf ([L][Mpad][Npad] each) for the gradient pass
-int svgp_elbo_keep_impl(hipStream_t s, int nb, int n, int m, int l, int p, int d, const double* X, int ldx,
-                        const double* Y, int ldy, const double* Z, int ldz, const double* thetas, const double* q_mu,
-                        const double* q_sqrt, const double* W, double noise, double scale, double jitter, void* ws,
-                        size_t ws_bytes, double* out, double* g_mu, double* g_var, int* info, const double* noise_dev,
-                        double* Aout, double* Bout) {
-    if (nb == 64)
-        return svgp_run<64>(s, n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, W, noise, scale, jitter,
-                            ws, ws_bytes, out, g_mu, g_var, info, nullptr, nullptr, noise_dev, Aout, Bout);
-    return svgp_run<32>(s, n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, W, noise, scale, jitter, ws,
-                        ws_bytes, out, g_mu, g_var, info, nullptr, nullptr, noise_dev, Aout, Bout);
-}
-
-int svgp_predict_impl(hipStream_t s, int nb, int n, int m, int l, int p, int d, const double* Xs, int ldx,
-                      const double* Z, int ldz, const double* thetas, const double* q_mu, const double* q_sqrt,
-                      const double* W, double jitter, void* ws, size_t ws_bytes, double* g_mu, double* g_var,
-                      double* f_mu, double* f_var, int* info) {
-    if (nb == 64)
-        return svgp_run<64>(s, n, m, l, p, d, Xs, ldx, Xs, 0, Z, ldz, thetas, q_mu, q_sqrt, W, 1.0, 1.0, jitter, ws,
-                            ws_bytes, nullptr, g_mu, g_var, info, f_mu, f_var);
-    return svgp_run<32>(s, n, m, l, p, d, Xs, ldx, Xs, 0, Z, ldz, thetas, q_mu, q_sqrt, W, 1.0, 1.0, jitter, ws,
-                        ws_bytes, nullptr, g_mu, g_var, info, f_mu, f_var);
+int svgp_predict_impl(int nb, const SvgpStreams& st, const SvgpProblem& P, const SvgpFwdOut& o) {
+    return TILE_CALL(nb, svgp_run, st, P, SvgpLik{}, o);
 }
 
 // ---------------------------------------------------------------- cached posterior (mfgp_posterior.hip)
@@ -761,60 +698,34 @@ static SvgpFactorLayout svgp_factor_layout(int nb, int m, int l, void* ws) {
     S.Tm = cdiv(m, nb);
     S.mpad = S.Tm * nb;
     const size_t mm = (size_t)S.mpad * S.mpad;
-    size_t off = 0;
-    char* base = (char*)ws;
-    auto take = [&](size_t count) {
-        off = (off + 255) & ~(size_t)255;
-        double* ptr = base ? reinterpret_cast<double*>(base + off) : nullptr;
-        off += count * sizeof(double);
-        return ptr;
-    };
-    S.Kuu = take(mm * l);
-    S.R = take(mm * l);
-    S.Dd = take((size_t)S.Tm * nb * nb * l);
-    S.ldiag = take((size_t)S.mpad * l);
-    S.Lq = take(mm * l);
-    S.bytes = off + 256;
+    Carve c(ws);
+    S.Kuu = c.take<double>(mm * l);
+    S.R = c.take<double>(mm * l);
+    S.Dd = c.take<double>((size_t)S.Tm * nb * nb * l);
+    S.ldiag = c.take<double>((size_t)S.mpad * l);
+    S.Lq = c.take<double>(mm * l);
+    S.bytes = c.off + 256;
     return S;
 }
 size_t svgp_posterior_factor_bytes(int nb, int m, int l) { return svgp_factor_layout(nb, m, l, nullptr).bytes; }
 
 template <int NB>
-static int svgp_factor_run(hipStream_t s, int m, int L, int d, const double* Z, int ldz, const double* thetas,
-                           const double* q_sqrt, double jitter, void* ws, size_t ws_bytes, double* Li, double* C,
-                           int* info) {
-    const SvgpFactorLayout S = svgp_factor_layout(NB, m, L, ws);
-    if (ws_bytes < S.bytes) return -2;
+static int svgp_factor_run(hipStream_t s, const SvgpProblem& P, double* Li, double* C) {
+    const int m = P.m, L = P.l;
+    const SvgpFactorLayout S = svgp_factor_layout(NB, m, L, P.ws);
+    if (P.ws_bytes < S.bytes) return -2;
     const long mm = (long)S.mpad * S.mpad;
-    GramArgs g{};
-    g.X1 = Z; g.ldx1 = ldz; g.sx1 = 0; g.n1 = m;
-    g.X2 = Z; g.ldx2 = ldz; g.sx2 = 0; g.n2 = m;
-    g.theta = thetas; g.stheta = theta_size(d); g.D = d; g.rbf_only = 0;
-    g.out = S.Kuu; g.ldo = S.mpad; g.so = mm;
-    g.padded = 1; g.npad = S.mpad; g.tiles_c = S.Tm; g.add_noise = 0; g.diag_add = jitter;
-    g.R = NB == 32 ? nullptr : S.R; g.ldr = S.mpad; g.sR = mm;
-    launch_gram_dense(g, L, S.mpad, S.mpad, s);
-    launch_first_factor<NB>(S.Kuu, S.mpad, mm, S.Dd, (long)S.Tm * NB * NB, S.ldiag, S.mpad, info, L, s);
-    CholArgs c{};
-    c.A = S.Kuu; c.lda = S.mpad; c.sA = mm;
-    c.R = S.R; c.ldr = S.mpad; c.sR = mm;
-    c.Xo = Li; c.ldx = S.mpad; c.sX = mm;
-    c.Dd = S.Dd; c.sD = (long)S.Tm * NB * NB; c.ldiag = S.ldiag; c.sL = S.mpad; c.info = info;
-    c.T = S.Tm; c.Tp = 0; c.k = 0;
-    c.r_implicit = NB == 32 ? 1 : 0;
-    launch_chol_steps<NB>(c, L, s);
+    launch_chol_steps<NB>(svgp_kuu_head<NB>(s, P, S, Li), L, s);
     hipLaunchKernelGGL(k_zero_upper_tiles, dim3(cdiv(S.mpad, ZU_ROWS), 1, L), dim3(256), 0, s, Li, NB, S.mpad, mm);
-    hipLaunchKernelGGL(k_lq_pad, dim3(cdiv(S.mpad, ZU_ROWS), 1, L), dim3(256), 0, s, q_sqrt, m, S.mpad, S.Lq, 0);
+    hipLaunchKernelGGL(k_lq_pad, dim3(cdiv(S.mpad, ZU_ROWS), 1, L), dim3(256), 0, s, P.q_sqrt, m, S.mpad, S.Lq,
+                       P.qs_packed);
     hipLaunchKernelGGL(k_lqt_linv<NB>, dim3(S.Tm * S.Tm, 1, L), dim3(NTHREADS), 2 * sizeof(double) * NB * (NB + 2), s,
                        S.Lq, Li, C, S.Tm);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-int svgp_posterior_factor(hipStream_t s, int nb, int m, int l, int d, const double* Z, int ldz, const double* thetas,
-                          const double* q_sqrt, double jitter, void* ws, size_t ws_bytes, double* Li, double* C,
-                          int* info) {
-    if (nb == 64) return svgp_factor_run<64>(s, m, l, d, Z, ldz, thetas, q_sqrt, jitter, ws, ws_bytes, Li, C, info);
-    return svgp_factor_run<32>(s, m, l, d, Z, ldz, thetas, q_sqrt, jitter, ws, ws_bytes, Li, C, info);
+int svgp_posterior_factor(int nb, hipStream_t s, const SvgpProblem& P, double* Li, double* C) {
+    return TILE_CALL(nb, svgp_factor_run, s, P, Li, C);
 }
 
 }  // namespace mfgp

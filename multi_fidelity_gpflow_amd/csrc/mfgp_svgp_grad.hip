@@ -1151,68 +1151,43 @@ static SvgpGradLayout grad_layout(int nb, int n, int m, int L, int p, int d, siz
     g.nb_uu = g.n_at * g.nbc_uu;
     g.nb_uf = g.n_at * g.nbc_uf;
     g.nnoise = 256;
-    size_t off = base_off;
-    char* base = (char*)ws;
-    auto take = [&](size_t count) {
-        off = (off + 255) & ~(size_t)255;
-        double* ptr = base ? reinterpret_cast<double*>(base + off) : nullptr;
-        off += count * sizeof(double);
-        return ptr;
-    };
-    g.qm = take((size_t)L * mpad);
-    g.alpha = take((size_t)L * npad);
-    g.beta = take((size_t)L * npad);
-    g.gqm = take((size_t)L * mpad);
-    g.Gb = take(mm * L);
-    g.H = take(mm * L);
-    g.P = take(mm * L);
-    g.Sig = take(mm * L);
-    g.T1 = take(mm * L);
-    g.A = take((size_t)mpad * npad * L);
-    g.B = take((size_t)mpad * npad * L);
-    g.gA = take((size_t)mpad * npad * L);
-    g.gLq = take(mm * L);
-    g.Kbar = take((size_t)mpad * npad * L);
-    g.r = take((size_t)n * p + 8);
-    g.gnp = take(g.nnoise);
-    g.gth_uu = take((size_t)L * g.nb_uu * G);
-    g.gth_uf = take((size_t)L * g.nb_uf * G);
-    g.gth_kff = take((size_t)L * G);
-    g.gz_uu = take((size_t)L * g.nb_uu * KG_ROWS * d + 8);
-    g.gz_uf = take((size_t)L * g.nb_uf * KG_ROWS * d + 8);
+    Carve c(ws);
+    c.off = base_off;
+    g.qm = c.take<double>((size_t)L * mpad);
+    g.alpha = c.take<double>((size_t)L * npad);
+    g.beta = c.take<double>((size_t)L * npad);
+    g.gqm = c.take<double>((size_t)L * mpad);
+    g.Gb = c.take<double>(mm * L);
+    g.H = c.take<double>(mm * L);
+    g.P = c.take<double>(mm * L);
+    g.Sig = c.take<double>(mm * L);
+    g.T1 = c.take<double>(mm * L);
+    g.A = c.take<double>((size_t)mpad * npad * L);
+    g.B = c.take<double>((size_t)mpad * npad * L);
+    g.gA = c.take<double>((size_t)mpad * npad * L);
+    g.gLq = c.take<double>(mm * L);
+    g.Kbar = c.take<double>((size_t)mpad * npad * L);
+    g.r = c.take<double>((size_t)n * p + 8);
+    g.gnp = c.take<double>(g.nnoise);
+    g.gth_uu = c.take<double>((size_t)L * g.nb_uu * G);
+    g.gth_uf = c.take<double>((size_t)L * g.nb_uf * G);
+    g.gth_kff = c.take<double>((size_t)L * G);
+    g.gz_uu = c.take<double>((size_t)L * g.nb_uu * KG_ROWS * d + 8);
+    g.gz_uf = c.take<double>((size_t)L * g.nb_uf * KG_ROWS * d + 8);
     g.het_rb = svgp_ve_het_rows(p, L);
     g.het_nwg = g.het_rb ? npad / g.het_rb : 0;   // npad is a multiple of nb >= 32, rb a power of two <= 16
-    g.hnp = take((size_t)g.het_nwg + 8);
+    g.hnp = c.take<double>((size_t)g.het_nwg + 8);
     g.msk_rb = svgp_ve_masked_rows(p, L);
     g.msk_nwg = g.msk_rb ? npad / g.msk_rb : 0;
-    g.hgw = take((size_t)std::max(g.het_nwg, g.msk_nwg) * 2 * p * L + 8);
-    g.mnp = take((size_t)g.msk_nwg * p + 8);
-    g.bytes = off + 256;
+    g.hgw = c.take<double>((size_t)std::max(g.het_nwg, g.msk_nwg) * 2 * p * L + 8);
+    g.mnp = c.take<double>((size_t)g.msk_nwg * p + 8);
+    g.bytes = c.off + 256;
     return g;
 }
-
-size_t svgp_workspace_bytes(int nb, int n, int m, int l, int p, int d);
 
 size_t svgp_grad_workspace_bytes(int nb, int n, int m, int l, int p, int d) {
     return grad_layout(nb, n, m, l, p, d, svgp_workspace_bytes(nb, n, m, l, p, d), nullptr).bytes;
 }
-
-int svgp_elbo_impl(hipStream_t s, int nb, int n, int m, int l, int p, int d, const double* X, int ldx,
-                   const double* Y, int ldy, const double* Z, int ldz, const double* thetas, const double* q_mu,
-                   const double* q_sqrt, const double* W, double noise, double scale, double jitter, void* ws,
-                   size_t ws_bytes, double* out, double* g_mu, double* g_var, int* info, const double* noise_dev);
-int svgp_elbo_keep_impl(hipStream_t s, int nb, int n, int m, int l, int p, int d, const double* X, int ldx,
-                        const double* Y, int ldy, const double* Z, int ldz, const double* thetas, const double* q_mu,
-                        const double* q_sqrt, const double* W, double noise, double scale, double jitter, void* ws,
-                        size_t ws_bytes, double* out, double* g_mu, double* g_var, int* info, const double* noise_dev,
-                        double* Aout, double* Bout);
-int svgp_predict_impl(hipStream_t s, int nb, int n, int m, int l, int p, int d, const double* Xs, int ldx,
-                      const double* Z, int ldz, const double* thetas, const double* q_mu, const double* q_sqrt,
-                      const double* W, double jitter, void* ws, size_t ws_bytes, double* g_mu, double* g_var,
-                      double* f_mu, double* f_var, int* info);
-// forward intermediates of svgp_run (mfgp_svgp.hip)
-void svgp_forward_buffers(int nb, int n, int m, int l, int p, int d, void* ws, double** Xo, double** C, double** Kuf,
-                          double** Lq, int* mpad, int* npad);
 
 template <int DC>
 static void launch_kgrad(hipStream_t s, const double* P1, long ld1, int n1, const double* P2, long ld2, int n2,
@@ -1226,28 +1201,28 @@ static void launch_kgrad(hipStream_t s, const double* P1, long ld1, int n1, cons
 }
 
 template <int NB>
-static int svgp_grad_run(hipStream_t s, int n, int m, int L, int p, int d, const double* X, int ldx, const double* Y,
-                         int ldy, const double* Z, int ldz, const double* thetas, const double* q_mu,
-                         const double* q_sqrt, const double* W, const double* noise_dev, double scale, double jitter,
-                         void* ws, size_t ws_bytes, double* out, double* g_mu, double* g_var, double* gZ,
-                         double* gtheta, double* gq_mu, double* gq_sqrt, double* gW, double* gnoise, int* info,
-                         double noise_host, double kl_mult) {
-    const size_t base = svgp_workspace_bytes(NB, n, m, L, p, d);
-    const SvgpGradLayout g = grad_layout(NB, n, m, L, p, d, base, ws);
-    if (ws_bytes < g.bytes) return -2;
+static int svgp_grad_run(const SvgpStreams& st, const SvgpProblem& P, const SvgpLik& lik, const SvgpFwdOut& o,
+                         const SvgpGradOut& go) {
+    const int n = P.n, m = P.m, L = P.l, p = P.p, d = P.d, ldx = P.ldx, ldy = P.ldy, ldz = P.ldz;
+    const double *X = P.X, *Y = P.Y, *Z = P.Z, *thetas = P.thetas, *W = P.W, *noise_dev = lik.noise_dev;
+    double *g_mu = o.g_mu, *g_var = o.g_var;
+    const double scale = P.scale;
+    const hipStream_t s = st.main;
+    const SvgpLayout S = svgp_layout(NB, n, m, L, p, d, P.ws);
+    const SvgpGradLayout g = grad_layout(NB, n, m, L, p, d, S.bytes, P.ws);
+    if (P.ws_bytes < g.bytes) return -2;
     // forward (fills Xo = Li, C = Lq^T Li, Kuf, Lq, A, B; g_mu / g_var; out = [elbo, KL, VE])
-    int rc = svgp_elbo_keep_impl(s, NB, n, m, L, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, W, noise_host,
-                                 scale, jitter, ws, ws_bytes, out, g_mu, g_var, info, noise_dev, g.A, g.B);
+    SvgpFwdOut fo = o;
+    fo.Aout = g.A; fo.Bout = g.B;
+    int rc = svgp_elbo_impl(NB, st, P, lik, fo);
     if (rc) return rc;
-    double *Li, *C, *Kuf, *Lq;
-    int mpad, npad;
-    svgp_forward_buffers(NB, n, m, L, p, d, ws, &Li, &C, &Kuf, &Lq, &mpad, &npad);
-    const int Tm = mpad / NB, Tn = npad / NB;
+    const double *Li = S.Xo, *Kuf = S.Kuf, *Lq = S.Lq;
+    const int mpad = S.mpad, npad = S.npad, Tm = S.Tm, Tn = S.Tn;
     const long mm = (long)mpad * mpad, mn = (long)mpad * npad;
-    const int G = theta_size(d);
+    const int G = S.G;
     // 1. VE backward (heteroscedastic: the fused row-tiled kernel and its dE/dW reduction)
-    const double* Yunc = svgp_side().Yunc;
-    const int pn = svgp_side().pn;
+    const double* Yunc = lik.kind == SvgpLik::HET ? lik.Yunc : nullptr;
+    const int pn = lik.kind == SvgpLik::MASKED ? lik.pn : 0;
     if (pn) {
         if (g.msk_rb == 0) return -4;
         const int ps = p | 1, ls = L | 1;
@@ -1255,11 +1230,11 @@ static int svgp_grad_run(hipStream_t s, int n, int m, int L, int p, int d, const
         const size_t smem = sizeof(double) * ((size_t)g.msk_rb * 3 * ps + (size_t)(g.msk_rb + 1) * 2 * L +
                                               (w_lds ? (size_t)p * ls : 0));
         hipLaunchKernelGGL(k_ve_bwd_masked, dim3(g.msk_nwg), dim3(NTHREADS), smem, s, g_mu, g_var, W, Y, (long)ldy, n, p,
-                           L, svgp_side().mnoise, pn, scale, npad, g.msk_rb, w_lds, g.r, g.alpha, g.beta, g.mnp, g.hgw);
+                           L, noise_dev, pn, scale, npad, g.msk_rb, w_lds, g.r, g.alpha, g.beta, g.mnp, g.hgw);
         if (W) hipLaunchKernelGGL(k_ve_het_reduce, dim3(cdv(p * L * VHR_LANES, 256)), dim3(256), 0, s, g.hgw, g.msk_nwg,
-                                  W, p * L, scale, gW);
+                                  W, p * L, scale, go.gW);
         hipLaunchKernelGGL(k_ve_masked_nreduce, dim3(pn == 1 ? 1 : cdv(p * VHR_LANES, NTHREADS)), dim3(NTHREADS), 0, s,
-                           g.mnp, g.msk_nwg, p, pn, gnoise);
+                           g.mnp, g.msk_nwg, p, pn, go.gnoise);
     } else if (Yunc) {
         if (g.het_rb == 0) return -4;
         const int ps = p | 1, ls = L | 1;
@@ -1267,19 +1242,19 @@ static int svgp_grad_run(hipStream_t s, int n, int m, int L, int p, int d, const
         const size_t smem = sizeof(double) * ((size_t)g.het_rb * 2 * ps + (size_t)(g.het_rb + 1) * 2 * L +
                                               (w_lds ? (size_t)p * ls : 0));
         hipLaunchKernelGGL(k_ve_bwd_het, dim3(g.het_nwg), dim3(NTHREADS), smem, s, g_mu, g_var, W, Y, (long)ldy, Yunc,
-                           (long)svgp_side().ldu, n, p, L, noise_dev, scale, npad, g.het_rb, w_lds, g.r, g.alpha,
+                           (long)lik.ldu, n, p, L, noise_dev, scale, npad, g.het_rb, w_lds, g.r, g.alpha,
                            g.beta, g.hnp, g.hgw);
         if (W) hipLaunchKernelGGL(k_ve_het_reduce, dim3(cdv(p * L * VHR_LANES, 256)), dim3(256), 0, s, g.hgw, g.het_nwg,
-                                  W, p * L, scale, gW);
+                                  W, p * L, scale, go.gW);
     } else {
         hipLaunchKernelGGL(k_ve_bwd, dim3(g.nnoise), dim3(NTHREADS), 0, s, g_mu, g_var, W, Y, (long)ldy, n, p, L,
                            noise_dev, scale, npad, g.r, g.alpha, g.beta, g.gnp);
         hipLaunchKernelGGL(k_ab, dim3(cdv(npad, 256), 1, L), dim3(256), 0, s, g.r, W, n, p, L, noise_dev, scale, npad,
                            g.alpha, g.beta);
         if (W) hipLaunchKernelGGL(k_gw, dim3(cdv(p * L, NTHREADS / 64)), dim3(NTHREADS), 0, s, g.r, g_mu, g_var, W, n, p,
-                                  L, noise_dev, scale, gW);
+                                  L, noise_dev, scale, go.gW);
     }
-    hipLaunchKernelGGL(k_qmu_pad, dim3(cdv(mpad, 256), 1, L), dim3(256), 0, s, q_mu, m, L, mpad, g.qm);
+    hipLaunchKernelGGL(k_qmu_pad, dim3(cdv(mpad, 256), 1, L), dim3(256), 0, s, P.q_mu, m, L, mpad, g.qm);
     // Two branches after gA (ONE fork, one join): the side takes dE/dm, dE/dLq, Kbar -> the (Z, X)
     // derivative sums and the K_diag term; the caller's stream Gb -> Sigma_bar -> the (Z, Z) sums.
     // (Forking before gA to run dE/dm / dE/dLq beside it, then handing Kbar to the side after gA
@@ -1300,12 +1275,12 @@ static int svgp_grad_run(hipStream_t s, int n, int m, int L, int p, int d, const
         a.Mt = Tm; a.Nt = Tn; a.Kt = Tm;
         bgemm<NB>(s, 0, 0, a, L);
     }
-    hipStream_t sb = svgp_fork(s);
+    hipStream_t sb = st.fork();
     // 2. dE/dm = A alpha - m  (folding its row products into step 3's epilogue, which reads A as
     //    Cin, measured slower: +45 us there and an 18 us partial reduction against this 51 us pass)
     hipLaunchKernelGGL(k_bmatvec, dim3(cdv(mpad, NTHREADS / 64), 1, L), dim3(NTHREADS), 0, sb, g.A, (long)npad, mn, 0,
-                       g.alpha, (long)npad, mpad, npad, 1.0, g.qm, (long)mpad, -kl_mult, g.gqm, (long)mpad);
-    hipLaunchKernelGGL(k_qmu_unpad, dim3(cdv(m, 256), 1, L), dim3(256), 0, sb, g.gqm, m, L, mpad, gq_mu);
+                       g.alpha, (long)npad, mpad, npad, 1.0, g.qm, (long)mpad, -P.kl_mult, g.gqm, (long)mpad);
+    hipLaunchKernelGGL(k_qmu_unpad, dim3(cdv(m, 256), 1, L), dim3(256), 0, sb, g.gqm, m, L, mpad, go.gq_mu);
     // 7. dE/dLq = tril(2 A diag(beta) B^T) - Lq + diag(1/Lq_ii)
     {
         BgemmArgs a{};
@@ -1383,32 +1358,23 @@ static int svgp_grad_run(hipStream_t s, int n, int m, int L, int p, int d, const
     else kgrad(std::integral_constant<int, 32>{});
     // the side's short tail
     hipLaunchKernelGGL(k_glq_final, dim3(std::min(cdv(m * m, 256), 1024), 1, L), dim3(256), 0, sb, g.gLq, Lq, m, mpad,
-                       mm, kl_mult, gq_sqrt, svgp_side().qs_packed);
+                       mm, P.kl_mult, go.gq_sqrt, P.qs_packed);
     hipLaunchKernelGGL(k_kff_grad, dim3(L), dim3(NTHREADS), 0, sb, X, (long)ldx, n, g.beta, npad, thetas, G, d,
                        g.gth_kff);
-    svgp_join(s);
+    st.join();
     const int tot = L * G + m * (d + 1) + 1;
     // masked: gnoise[pn] is k_ve_masked_nreduce's; the scalar noise sum here is over no partials and goes
     // to the spare entry behind mnp
-    double* gn_scalar = pn ? g.mnp + (size_t)g.msk_nwg * p : gnoise;
+    double* gn_scalar = pn ? g.mnp + (size_t)g.msk_nwg * p : go.gnoise;
     hipLaunchKernelGGL(k_grad_reduce, dim3(cdv(tot * GR_LANES, 256)), dim3(256), 0, s, g.gth_uu, g.nb_uu, g.gth_uf, g.nb_uf,
                        g.gth_kff, g.gz_uu, g.gz_uf, g.n_at, g.nbc_uu, g.nbc_uf, L, G, d, m, Yunc ? g.hnp : g.gnp,
-                       pn ? 0 : (Yunc ? g.het_nwg : g.nnoise), gtheta, gZ, gn_scalar);
+                       pn ? 0 : (Yunc ? g.het_nwg : g.nnoise), go.gtheta, go.gZ, gn_scalar);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-int svgp_grad_impl(hipStream_t s, int nb, int n, int m, int l, int p, int d, const double* X, int ldx, const double* Y,
-                   int ldy, const double* Z, int ldz, const double* thetas, const double* q_mu, const double* q_sqrt,
-                   const double* W, const double* noise_dev, double noise_host, double scale, double kl_mult,
-                   double jitter, void* ws, size_t ws_bytes, double* out, double* g_mu, double* g_var, double* gZ,
-                   double* gtheta, double* gq_mu, double* gq_sqrt, double* gW, double* gnoise, int* info) {
-    if (nb == 64)
-        return svgp_grad_run<64>(s, n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, W, noise_dev, scale,
-                                 jitter, ws, ws_bytes, out, g_mu, g_var, gZ, gtheta, gq_mu, gq_sqrt, gW, gnoise, info,
-                                 noise_host, kl_mult);
-    return svgp_grad_run<32>(s, n, m, l, p, d, X, ldx, Y, ldy, Z, ldz, thetas, q_mu, q_sqrt, W, noise_dev, scale,
-                             jitter, ws, ws_bytes, out, g_mu, g_var, gZ, gtheta, gq_mu, gq_sqrt, gW, gnoise, info,
-                             noise_host, kl_mult);
+int svgp_grad_impl(int nb, const SvgpStreams& st, const SvgpProblem& P, const SvgpLik& lik, const SvgpFwdOut& o,
+                   const SvgpGradOut& go) {
+    return TILE_CALL(nb, svgp_grad_run, st, P, lik, o, go);
 }
 
 // ---------------------------------------------------------------- predict with covariances
@@ -1463,31 +1429,24 @@ size_t svgp_predict_cov_workspace_bytes(int nb, int ns, int m, int l, int p, int
 }
 
 template <int NB>
-static int svgp_predict_cov_run(hipStream_t s, int mode, int ns, int m, int L, int p, int d, const double* Xs,
-                                int ldx, const double* Z, int ldz, const double* thetas, const double* q_mu,
-                                const double* q_sqrt, const double* W, double jitter, void* ws, size_t ws_bytes,
-                                double* g_mu, double* g_var, double* f_mu, double* f_var, double* f_cov, int* info) {
-    if (ws_bytes < svgp_predict_cov_workspace_bytes(NB, ns, m, L, p, d)) return -2;
-    int rc = svgp_predict_impl(s, NB, ns, m, L, p, d, Xs, ldx, Z, ldz, thetas, q_mu, q_sqrt, W, jitter, ws, ws_bytes,
-                               g_mu, g_var, f_mu, f_var, info);
+static int svgp_predict_cov_run(const SvgpStreams& st, const SvgpProblem& P, const SvgpFwdOut& o, const SvgpCovOut& co) {
+    const int ns = P.n, m = P.m, L = P.l, p = P.p, d = P.d, ldx = P.ldx, mode = co.mode;
+    const double *Xs = P.X, *thetas = P.thetas;
+    const hipStream_t s = st.main;
+    if (P.ws_bytes < svgp_predict_cov_workspace_bytes(NB, ns, m, L, p, d)) return -2;
+    int rc = svgp_predict_impl(NB, st, P, o);
     if (rc) return rc;
-    double *Li, *C, *Kuf, *Lq;
-    int mpad, npad;
-    svgp_forward_buffers(NB, ns, m, L, p, d, ws, &Li, &C, &Kuf, &Lq, &mpad, &npad);
-    const int Tm = mpad / NB, Tn = npad / NB;
+    const SvgpLayout S = svgp_layout(NB, ns, m, L, p, d, P.ws);
+    const double *Li = S.Xo, *C = S.C, *Kuf = S.Kuf;
+    const int mpad = S.mpad, npad = S.npad, Tm = S.Tm, Tn = S.Tn;
     const long mm = (long)mpad * mpad, mn = (long)mpad * npad, nn = (long)npad * npad;
-    size_t off = (svgp_workspace_bytes(NB, ns, m, L, p, d) + 255) & ~(size_t)255;
-    auto take = [&](size_t count) {
-        off = (off + 255) & ~(size_t)255;
-        double* q = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + off);
-        off += count * sizeof(double);
-        return q;
-    };
-    double* F1 = take((size_t)L * mm);
-    double* F = take((size_t)L * mm);
-    double* Tk = take((size_t)L * mn);
-    double* Knn = take((size_t)L * nn);
-    double* G = take((size_t)L * nn);
+    Carve c(P.ws);
+    c.off = S.bytes;
+    double* F1 = c.take<double>((size_t)L * mm);
+    double* F = c.take<double>((size_t)L * mm);
+    double* Tk = c.take<double>((size_t)L * mn);
+    double* Knn = c.take<double>((size_t)L * nn);
+    double* G = c.take<double>((size_t)L * nn);
     if (mode != 2) {
         sq<NB>(s, Tm, L, mm, mpad, 1, C, 0, C, F1);                   // C^T C
         sq<NB>(s, Tm, L, mm, mpad, 1, Li, 0, Li, F, -1.0, F1, 1.0, 0, nullptr, nullptr, 0, 2, 1);   // F = C^T C - Li^T Li
@@ -1519,19 +1478,13 @@ static int svgp_predict_cov_run(hipStream_t s, int mode, int ns, int m, int L, i
     }
     const long tot = mode == 1 ? (long)p * ns * ns : (mode == 2 ? (long)ns * p * p : (long)ns * ns * p * p);
     hipLaunchKernelGGL(k_svgp_mix_cov, dim3((unsigned)std::min<long>(cdv((int)std::min<long>(tot, 1L << 30), 256), 4096)),
-                       dim3(256), 0, s, mode, ns, p, L, W, g_var, G, (long)npad, nn, f_cov);
+                       dim3(256), 0, s, mode, ns, p, L, P.W, o.g_var, G, (long)npad, nn, co.f_cov);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-int svgp_predict_cov_impl(hipStream_t s, int nb, int mode, int ns, int m, int l, int p, int d, const double* Xs,
-                          int ldx, const double* Z, int ldz, const double* thetas, const double* q_mu,
-                          const double* q_sqrt, const double* W, double jitter, void* ws, size_t ws_bytes,
-                          double* g_mu, double* g_var, double* f_mu, double* f_var, double* f_cov, int* info) {
-    if (nb == 64)
-        return svgp_predict_cov_run<64>(s, mode, ns, m, l, p, d, Xs, ldx, Z, ldz, thetas, q_mu, q_sqrt, W, jitter, ws,
-                                        ws_bytes, g_mu, g_var, f_mu, f_var, f_cov, info);
-    return svgp_predict_cov_run<32>(s, mode, ns, m, l, p, d, Xs, ldx, Z, ldz, thetas, q_mu, q_sqrt, W, jitter, ws,
-                                    ws_bytes, g_mu, g_var, f_mu, f_var, f_cov, info);
+int svgp_predict_cov_impl(int nb, const SvgpStreams& st, const SvgpProblem& P, const SvgpFwdOut& o,
+                          const SvgpCovOut& co) {
+    return TILE_CALL(nb, svgp_predict_cov_run, st, P, o, co);
 }
 
 // ---------------------------------------------------------------- packed Adam (training step)

@@ -238,6 +238,45 @@ def test_c_entries_reject_a_bad_pn_before_any_device_work():
         lib.mfgp_destroy(h)
 
 
+def test_c_entries_reject_a_short_leading_dimension_before_any_device_work():
+    """All six ELBO entries, value and gradient alike, return the bad-argument code (-1) for ldx < d + 1,
+    ldz < d + 1, ldy < p and, with a non-null Yunc, ldu < p (include/mfgp.h): such a call would read
+    past its rows.  Non-null dummy pointers, never read, as above."""
+    import ctypes as C
+    from multi_fidelity_gpflow_amd import _lib
+    from multi_fidelity_gpflow_amd.build import build_lib
+    build_lib()
+    lib = _lib.load()
+    h = C.c_void_p()
+    assert lib.mfgp_create(0, C.byref(h)) == 0
+    try:
+        q = 64   # never dereferenced
+        n, m, l, p, d = 8, 4, 3, 3, 2
+        val = (1.0, 1e-6, q, 1 << 20, q, q, q, q)                             # scale .. info
+        grad = (1.0, 1.0, 1e-6, q, 1 << 20, q, q, q, q, q, q, q, None, q, q)  # scale, kl_mult .. info
+
+        def entries(ldx, ldy, ldz, yunc=None, ldu=p):
+            head = (h, n, m, l, p, d, q, ldx, q, ldy)
+            z = (q, ldz, q, q, q)   # Z, ldz, thetas, q_mu, q_sqrt
+            return {   # called one by one: only a call with a bad argument may be made on these pointers
+                "elbo": lambda: lib.mfgp_svgp_elbo(*head, *z, None, 0.1, *val),
+                "elbo_grad": lambda: lib.mfgp_svgp_elbo_grad(*head, *z, None, q, *grad),
+                "elbo_het": lambda: lib.mfgp_svgp_elbo_het(*head, yunc, ldu, *z, None, 0.1, *val),
+                "elbo_grad_het": lambda: lib.mfgp_svgp_elbo_grad_het(*head, yunc, ldu, *z, 0, None, q, *grad),
+                "elbo_masked": lambda: lib.mfgp_svgp_elbo_masked(*head, *z, None, q, p, *val),
+                "elbo_grad_masked": lambda: lib.mfgp_svgp_elbo_grad_masked(*head, *z, 0, None, q, p, *grad),
+            }
+
+        for lds in ((d, p, d + 1), (d + 1, p, d), (d + 1, p - 1, d + 1)):   # ldx, ldy, ldz: one short each
+            for yunc in (None, q):
+                for name, call in entries(*lds, yunc=yunc).items():
+                    assert call() == -1, (name, lds, yunc)
+        short_ldu = entries(d + 1, p, d + 1, yunc=q, ldu=p - 1)
+        assert short_ldu["elbo_het"]() == -1 and short_ldu["elbo_grad_het"]() == -1
+    finally:
+        lib.mfgp_destroy(h)
+
+
 def test_multiple_assign_restores_values_whose_unconstrained_value_is_near_zero():
     """A Softplus value near log 2 has u ~ 0, where an ulp of u is a hundredth of an ulp of the value:
     trained (P,) variances around 0.7 are such values.  multiple_assign restores every one bit for bit."""
