@@ -763,15 +763,15 @@ __device__ __forceinline__ int graph_source(double f, int m) {
     return -1;
 }
 // one RBF term of source s between raw rows xa, xb
-// graph_k with the source's inverse squared lengthscales il2[0..D) precomputed
-__device__ __forceinline__ double graph_k_il2(const double* xa, const double* xb, int s, const GraphTheta& th,
-                                              const double* il2) {
+// graph_k without its variance, exp(-r2/2) = dk_s/dv_s, with the source's inverse squared
+// lengthscales il2[0..D) precomputed
+__device__ __forceinline__ double graph_e_il2(const double* xa, const double* xb, int D, const double* il2) {
     double r2 = 0.0;
-    for (int d = 0; d < th.D; ++d) {
+    for (int d = 0; d < D; ++d) {
         const double q = xa[d] - xb[d];
         r2 += q * q * il2[d];
     }
-    return th.v(s) * exp(-0.5 * r2);
+    return exp(-0.5 * r2);
 }
 __device__ __forceinline__ double graph_k(const double* xa, const double* xb, int s, const GraphTheta& th) {
     double r2 = 0.0;

@@ -1270,7 +1270,7 @@ __global__ __launch_bounds__(NTHREADS) void k_grad(GradArgs a) {
         // (i > j) also carries the mirrored entry K_ba, which differs in the LF-LF block.
         const GraphTheta gt{a.theta, a.D, a.nlf};
         const int m = a.nlf;
-        double co[MFGP_MAX_LF + 1][NE];       // per element: 1/2 W * dK/dk_s * k_s
+        double co[MFGP_MAX_LF + 1][NE];       // per element: 1/2 W * dK/dk_s * exp(-r2_s / 2)
         double grho[MFGP_MAX_LF], grl[MFGP_MAX_LF * MFGP_MAX_LF];
         double gn = 0.0;
 #pragma unroll
@@ -1288,27 +1288,30 @@ __global__ __launch_bounds__(NTHREADS) void k_grad(GradArgs a) {
 #pragma unroll
                 for (int s2 = 0; s2 <= MFGP_MAX_LF; ++s2) co[s2][e] = 0.0;
                 if (sa >= 0 && sb >= 0) {
-                    double ks[MFGP_MAX_LF + 1];
+                    // dk_s/dv_s = exp(-r2/2), the autodiff of v * exp(-r2/2): co carries es, and the
+                    // variance enters only where k_s itself is needed, so the v_s entries stay
+                    // finite where a variance is 0 (K / v gave 0/0 there, as in the linear epilogue)
+                    double es[MFGP_MAX_LF + 1];
                     for (int s2 = 0; s2 <= m; ++s2)
-                        ks[s2] = graph_k_il2(xi + ri * XS, xj + cj * XS, s2, gt, il2 + s2 * a.D);
+                        es[s2] = graph_e_il2(xi + ri * XS, xj + cj * XS, a.D, il2 + s2 * a.D);
                     auto accum = [&](int s1, int t1) {   // entry with row source s1, column source t1
                         if (s1 < m && t1 < m) {
-                            if (s1 == t1) co[s1][e] += w * ks[s1];
+                            if (s1 == t1) co[s1][e] += w * es[s1];
                             else {
-                                co[s1][e] += w * gt.rhoLF(s1, t1) * ks[s1];
-                                grl[s1 * m + t1] += w * ks[s1];
+                                co[s1][e] += w * gt.rhoLF(s1, t1) * es[s1];
+                                grl[s1 * m + t1] += w * (gt.v(s1) * es[s1]);
                             }
                         } else if (s1 < m || t1 < m) {
                             const int u = (s1 < m) ? s1 : t1;
-                            co[u][e] += w * gt.rho(u) * ks[u];
-                            grho[u] += w * ks[u];
+                            co[u][e] += w * gt.rho(u) * es[u];
+                            grho[u] += w * (gt.v(u) * es[u]);
                         } else {
                             for (int k2 = 0; k2 < m; ++k2) {
                                 const double rr = gt.rho(k2);
-                                co[k2][e] += w * rr * rr * ks[k2];
-                                grho[k2] += w * 2.0 * rr * ks[k2];
+                                co[k2][e] += w * rr * rr * es[k2];
+                                grho[k2] += w * 2.0 * rr * (gt.v(k2) * es[k2]);
                             }
-                            co[m][e] += w * ks[m];
+                            co[m][e] += w * es[m];
                         }
                     };
                     accum(sa, sb);
@@ -1341,8 +1344,7 @@ __global__ __launch_bounds__(NTHREADS) void k_grad(GradArgs a) {
         reduce_entries([&](int qx, double v) {
             if (qx < ro) {
                 const int s2 = qx / (1 + a.D), d = qx % (1 + a.D);
-                if (d == 0) v /= gt.v(s2);
-                else { const double l = gt.l(s2, d - 1); v /= l * l * l; }
+                if (d != 0) { const double l = gt.l(s2, d - 1); v *= gt.v(s2) / (l * l * l); }
             }
             return v;
         });

@@ -7,8 +7,14 @@ TF's _CholeskyGrad, and the LF-LF block is differentiated entry by entry, so the
 asymmetric rho_LF block gets the reference's gradient).  Adam restated as TF 2.10
 Keras legacy Adam with a constant float32 learning rate.
 
-Parity: UNPINNED by reference outputs — the reference ships no test, notebook or
-recorded value for the graph model; this restates graph.py line by line.
+Parity: the reference ships no test, notebook or recorded value for the graph model;
+this restates graph.py line by line.  It is pinned where it can be: with one LF source
+(m = 1) graph.py:59-91 is linear.py:93-102 plus the 1e-6 I jitter (rho_LF drops out at
+i == j, rho[:, 0] is rho), and tests/test_graph_oracle_pin.py holds lml, its autograd
+gradient and predict_f here to oracle/mfgp_oracle.py -- itself pinned by the reference's
+recorded values -- at noise + 1e-6 on HBS and Goku (LML 1e-12, gradient and predictions
+1e-11).  Still unpinned: the cross-source rho_LF terms of the LF-LF block, which exist
+only at m >= 2 and which no reference output covers.
 """
 from __future__ import annotations
 

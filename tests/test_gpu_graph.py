@@ -1,10 +1,19 @@
 """GraphMultiFidelityKernel / GraphMultiFidelityGPModel (mfgpflow/graph.py)
 on the HIP path vs. the torch-CPU restatement oracle/graph_oracle.py.
 
-Parity is UNPINNED by reference outputs (the reference has no graph-model test or recorded
-value); the oracle restates graph.py line by line, including its asymmetric LF-LF block
-(rho_LF[i, j] k_i) and the 1e-6 jitter inside K.  Tolerances: K entries 1e-13 abs; LML
-1e-11 rel; gradient 1e-8 rel of the largest component; Adam trajectory 1e-9 rel."""
+Parity: the reference has no graph-model test or recorded value; the oracle restates graph.py
+line by line, including its asymmetric LF-LF block (rho_LF[i, j] k_i) and the 1e-6 jitter inside
+K.  What is pinned all the same: with one LF source the graph kernel is the linear kernel plus
+1e-6 I, so tests/test_graph_oracle_pin.py holds graph_oracle, and tests/test_gpu_graph_paths.py
+the HIP path, to oracle/mfgp_oracle.py (pinned by the reference's recorded values) on HBS and
+Goku.  That covers every term of K, the LML, its gradient and predict_f except the cross-source
+rho_LF terms, which exist only at m >= 2 and which no reference output covers: those rest on the
+line-by-line restatement alone.
+
+This file runs one shape family (n = 82, D = 3, m <= 3, tile 32, rows sorted by source: the
+launch-per-step Cholesky); test_gpu_graph_paths.py runs the flow schedule, tile 64, m = 4, other D
+and unsorted rows.  Tolerances: K entries 1e-13 abs; LML 1e-11 rel; gradient 1e-8 rel of the
+largest component; Adam trajectory 1e-9 rel."""
 import numpy as np
 import pytest
 import torch
