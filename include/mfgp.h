@@ -497,6 +497,36 @@ int mfgp_gpr_posterior_design_append(mfgp_handle_t h, int nlf, int n, int p, int
                                      size_t cache_bytes, const double* Xall, int ldx, int nref, int ncand, void* ws,
                                      size_t ws_bytes, const int* pick, double* E, int ldE, int k);
 
+/* Block append to a GPR cache: the cache of the n + k rows [X ; Xadd], [Y ; Yadd] at the cached
+ * hyper-parameters, from the cached factors in O(n^2 k) (no Gram of X, no factorization of K), for
+ * nlf = 0 and nlf > 0 alike.  1 <= k <= 32.
+ *   Xadd      [k x (d + 1)] (ldxa), fidelity in the last column.
+ *   Yadd      [k x p] (ldya), or NULL: the rows are observed at the cache's own mean at Xadd (a
+ *             fantasy): their rows of Z are exactly zero, the mean of the new cache is the old one
+ *             and its variance is that of a refit.
+ *   out_cache the new block, laid out as mfgp_gpr_posterior_build lays out n + k rows
+ *             (mfgp_gpr_posterior_size(n + k) bytes); every byte of it is written.  It must not be
+ *             `cache`, which is only read.
+ *   mean_add  [k x p] (ldm; may be NULL): the old cache's mean at Xadd.
+ *   info      one int: 0; -(r + 1) when row r of Xadd has a fidelity that is no source of the kernel;
+ *             the 1-based first non-positive or non-finite pivot of S = K(Xadd, Xadd) + s2 I - A^T A
+ *             otherwise.  The new block is not usable unless info is 0.
+ * With B the cross block as a factorization of the stacked rows reads it (graph kernel: the new row
+ * is the row argument of the entry function; the 1e-6 jitter on the diagonal of K(Xadd, Xadd)):
+ * A = L^{-1} B^T, S = L22 L22^T, R = L22^{-1}, new L^{-1} = [L^{-1} 0 ; -R A^T L^{-1}  R], new
+ * Z = [Z ; R (Yadd - A^T Z)].  Four launches: the predict call's two on Xadd, one workgroup for S, R and
+ * W = -R A^T, and one pass over the cached tiles that copies each to the new row stride and multiplies
+ * it into the bottom rows.  Fixed-order sums and no floating-point atomics (the same inputs give the
+ * same bits); nothing is allocated, no synchronisation, no host read of a device word.  k outside
+ * 1..32, a bad geometry or out_cache == cache: MFGP_ERR_ARG; cache, out_cache or ws smaller than the
+ * *_size calls report: MFGP_ERR_WORKSPACE; both before any device work.  Use the cache at the tile
+ * size it was built for. */
+int mfgp_gpr_posterior_append_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int k, size_t* bytes);
+int mfgp_gpr_posterior_append(mfgp_handle_t h, int nlf, int n, int p, int d, int k, const void* cache,
+                              size_t cache_bytes, const double* Xadd, int ldxa, const double* Yadd, int ldya, void* ws,
+                              size_t ws_bytes, void* out_cache, size_t out_bytes, double* mean_add, int ldm,
+                              int* info);
+
 /* Diagnostic: one v_mfma_f64_16x16x4_f64 with A[i][k] = 4i+k+1, B[k][j] = 100k+j;
  * writes C (16x16 row-major, device). */
 int mfgp_selftest_mfma(mfgp_handle_t h, double* out);

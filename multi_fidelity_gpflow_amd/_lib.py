@@ -106,6 +106,8 @@ SIGNATURES = {
     "mfgp_gpr_posterior_design_workspace_size": [_p, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_sz)],
     "mfgp_gpr_posterior_design_score": [_p, _i, _i, _i, _i, _p, _sz, _p, _i, _i, _i, _p, _p, _i, _i, _p, _sz, _p, _i],
     "mfgp_gpr_posterior_design_append": [_p, _i, _i, _i, _i, _p, _sz, _p, _i, _i, _i, _p, _sz, _p, _p, _i, _i],
+    "mfgp_gpr_posterior_append_workspace_size": [_p, _i, _i, _i, _i, _i, C.POINTER(_sz)],
+    "mfgp_gpr_posterior_append": [_p, _i, _i, _i, _i, _i, _p, _sz, _p, _i, _p, _i, _p, _sz, _p, _sz, _p, _i, _p],
     "mfgp_selftest_mfma": [_p, _p],
     # dtype-generic forms (MFGP_F64 = 0, MFGP_F32 = 1)
     "mfgp_set_f32_panel": [_p, _i],

@@ -185,32 +185,6 @@ __global__ __launch_bounds__(NTHREADS) void k_design_score(DesignArgs a) {
     }
 }
 
-// K(xa, xb) of one pair of stacked rows (fidelity in column D): post_mf_tile's expressions for the
-// linear multi-fidelity kernel, the graph entry function (row source first) for nlf > 0
-__device__ __forceinline__ double design_entry(const double* xa, const double* xb, int D, int nlf,
-                                               const double* theta) {
-    if (nlf) {
-        const GraphTheta th{theta, D, nlf};
-        return graph_entry(xa, xb, graph_source(xa[D], nlf), graph_source(xb[D], nlf), th);
-    }
-    const double fa = xa[D], fb = xb[D];
-    const bool La = (fa == 0.0), Ha = (fa == 1.0), Lb = (fb == 0.0), Hb = (fb == 1.0);
-    if (!(La || Ha) || !(Lb || Hb)) return 0.0;
-    double e[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int d = 0; d < D; ++d) {
-        const double df = xa[d] - xb[d];
-        const double qL = df * rcp_nr(theta[1 + d]), qD = df * rcp_nr(theta[2 + D + d]);
-        e[0] += qL * qL;
-        e[1] += qD * qD;
-    }
-    e[0] *= -0.5;
-    e[1] *= -0.5;
-    exp4(e);
-    const double vL = theta[0], vD = theta[1 + D], rho = theta[2 + 2 * D];
-    const double kL = vL * e[0];
-    return (La && Lb) ? kL : (!(Ha && Hb) ? kL * rho : kL * (rho * rho) + vD * e[1]);
-}
-
 __global__ __launch_bounds__(NTHREADS) void k_design_row(DesignArgs a) {
     __shared__ double ac[DESIGN_RROWS];   // the picked candidate's column of A, this chunk's rows
     __shared__ int last;

@@ -224,6 +224,9 @@ struct PostArgs {
     double* glat;                             // [batch][Ts][D][NB] per batch entry sums (batch > 1)
     int* gcnt;                                // k_post_grad's arrival counters: [Ts], then [batch][Ts] (zeroed by k_post_a)
     double* gX; long ldgx;                    // [nstar x (D + 1)], fidelity column written as 0
+    // graph kernel: 1 generates K as graph_entry(X* row, cached row), the block a factorization reads when the
+    // X* rows are appended BELOW the cached ones (mfgp_append.hip); 0: graph_entry(cached row, X* row)
+    int swap;
 };
 // tasks of one batch entry: row tile i has ceil((full ? T : i + 1) / chunk) of them
 int post_ntasks(int T, int chunk, int full);
@@ -258,6 +261,34 @@ struct LoArgs {
     int* info;                                // [ngroups]
 };
 void launch_leave_out(const LoArgs& a, hipStream_t s);
+
+// Block append to the GPR cache (mfgp_append.hip): k <= 32 rows Xadd under the cached factors.  The forward
+// (launch_post with PostArgs::swap, A kept) has run on Xadd; k_append_head forms S = K(Xadd, Xadd) + s2 I - A^T A,
+// factors it (R = L22^{-1}), writes W = -R A^T, the new rows of Z and info; k_append_rows copies the old
+// block's L^{-1} tiles to the new block's row stride and multiplies them into the new bottom rows W L^{-1}.
+constexpr int APPEND_MAXK = 32;
+struct AppendArgs {
+    const double* LZ; long ldr;               // old block: [L^{-1} | Z] rows (read-only)
+    const double* X; const double* theta;     // old block: inputs [n x (D + 1)], kernel parameters [G]
+    int n, npad, T;                           // old rows, padded rows, row tiles
+    int p, ppad, D, nlf, G, k;
+    double diag_add;                          // the graph kernel's jitter on the diagonal of K (0: linear kernel)
+    const double* Xadd; long ldxa;            // [k x (D + 1)]
+    const double* Yadd; long ldya;            // [k x p]; nullptr: the rows are observed at their own mean
+    const double* Am; long ldam;              // A = L^{-1} K(X, Xadd), npad x ldam (kept by the forward)
+    const double* mean; long ldm;             // the forward's mean at Xadd [k x p]
+    double* W;                                // [32][npad]  -R A^T (rows >= k zero)
+    double* Rw;                               // [32][32]    R, zero above the diagonal, identity beyond k
+    int* cnt;                                 // [T] arrival counters of k_append_rows (zeroed by the head)
+    double* part;                             // [ntask][32 * NB] partial bottom products
+    int chunk, ntask, nfill;                  // row tiles per task, tasks, workgroups of the fill pass
+    double* LZo; long ldro; int npado;        // new block: [L^{-1} | Z], n + k rows padded to npado
+    double* Xo; double* thetao;
+    unsigned char* obase; long gap0[3], gap1[3];   // new block: the bytes no array covers (zeroed)
+    int* info;
+};
+int append_ntasks(int T, int chunk);
+template <int NB> void launch_append(const AppendArgs& a, hipStream_t s);
 
 // Simulation design from the GPR cache (mfgp_design.hip).  The forward (launch_post, A kept) has run on
 // the stacked points [Xref ; Xcand]; k_design_score forms C = K(Xref, Xcand) - A_ref^T A_cand -

@@ -1,6 +1,7 @@
 // Device helpers shared by the kernels that work on the cached posterior's A = L^{-1} K(X, X*)
-// (mfgp_posterior.hip, mfgp_design.hip): the LDS staging constants, the K(X, X*) tile generator of the
-// linear multi-fidelity kernel, K_diag of one row and the fixed-order sums of cross-workgroup partials.
+// (mfgp_posterior.hip, mfgp_design.hip, mfgp_append.hip): the LDS staging constants, the K(X, X*) tile generator of the
+// linear multi-fidelity kernel, the kernel entry of one pair of rows, K_diag of one row and the fixed-order
+// sums of cross-workgroup partials.
 #pragma once
 #include "mfgp_device.h"
 
@@ -74,6 +75,32 @@ __device__ __forceinline__ double post_kdiag(double f, const double* theta, int 
     const MFTheta th{theta, D};
     const double rho = th.rho();
     return (f == 0.0) ? th.vL() : ((f == 1.0) ? th.vL() * (rho * rho) + th.vD() : 0.0);
+}
+
+// K(xa, xb) of one pair of stacked rows (fidelity in column D): post_mf_tile's expressions for the
+// linear multi-fidelity kernel, the graph entry function (row source first) for nlf > 0
+__device__ __forceinline__ double design_entry(const double* xa, const double* xb, int D, int nlf,
+                                               const double* theta) {
+    if (nlf) {
+        const GraphTheta th{theta, D, nlf};
+        return graph_entry(xa, xb, graph_source(xa[D], nlf), graph_source(xb[D], nlf), th);
+    }
+    const double fa = xa[D], fb = xb[D];
+    const bool La = (fa == 0.0), Ha = (fa == 1.0), Lb = (fb == 0.0), Hb = (fb == 1.0);
+    if (!(La || Ha) || !(Lb || Hb)) return 0.0;
+    double e[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int d = 0; d < D; ++d) {
+        const double df = xa[d] - xb[d];
+        const double qL = df * rcp_nr(theta[1 + d]), qD = df * rcp_nr(theta[2 + D + d]);
+        e[0] += qL * qL;
+        e[1] += qD * qD;
+    }
+    e[0] *= -0.5;
+    e[1] *= -0.5;
+    exp4(e);
+    const double vL = theta[0], vD = theta[1 + D], rho = theta[2 + 2 * D];
+    const double kL = vL * e[0];
+    return (La && Lb) ? kL : (!(Ha && Hb) ? kL * rho : kL * (rho * rho) + vD * e[1]);
 }
 
 // sum over k < n of base[k * stride] in k order; the sc1 loads are issued eight at a time (one at a

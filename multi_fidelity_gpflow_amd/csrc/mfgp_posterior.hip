@@ -134,8 +134,9 @@ __global__ __launch_bounds__(NTHREADS) void k_post_a(PostArgs a) {
         if (a.nlf) {
             for (int e = t; e < NB * NB; e += NTHREADS) {
                 const int r = e / NB, c = e % NB;
-                Ks[r * S + c] = graph_entry(x1 + r * PXS, xs + c * PXS, graph_source(f1[r], a.nlf),
-                                            graph_source(fs[c], a.nlf), gth);
+                const int s1 = graph_source(f1[r], a.nlf), s2 = graph_source(fs[c], a.nlf);
+                Ks[r * S + c] = a.swap ? graph_entry(xs + c * PXS, x1 + r * PXS, s2, s1, gth)
+                                       : graph_entry(x1 + r * PXS, xs + c * PXS, s1, s2, gth);
             }
         } else {
             post_mf_tile<NB>(Ks, x1, f1, xs, fs, D, il, ths);

@@ -1,7 +1,7 @@
 // C-ABI entry points of the cached posterior (include/mfgp.h, mfgp_gpr_posterior_size through
 // mfgp_svgp_posterior_predict_vjp): the cache and workspace layouts, the argument blocks and the launch
-// sequences of mfgp_posterior.hip / mfgp_leave_out.hip / mfgp_design.hip.  Host-side orchestration only, as
-// mfgp_capi.hip: no allocation, no synchronisation.
+// sequences of mfgp_posterior.hip / mfgp_leave_out.hip / mfgp_design.hip / mfgp_append.hip.  Host-side
+// orchestration only, as mfgp_capi.hip: no allocation, no synchronisation.
 #include <algorithm>
 
 #include "mfgp_device.h"
@@ -257,6 +257,72 @@ static int gpr_posterior_design_impl(mfgp_handle_t h, int nlf, int n, int p, int
     return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
 }
 
+// Append workspace: the predict layout of the k new rows without its covariance blocks (A is kept
+// there), the forward's mean and var, then W, R, the row kernel's counters and its partials.  Tasks: 4
+// row tiles of a tile column (at Goku's 37 tiles 190 tasks, the longest four products), longer beyond
+// 128 tiles so that a column's last workgroup sums at most 32 partials.
+struct AppendLayout {
+    PostLayout P;
+    int chunk, ntask, nfill;
+    double *mean, *var, *W, *Rw, *part;
+    int* cnt;
+    size_t bytes;
+};
+static AppendLayout append_layout(int nb, const GprCache& c, int k, void* ws) {
+    AppendLayout L{};
+    L.P = post_layout(nb, c.T, c.Tp, k, 1, false, ws, false);
+    const size_t o = (L.P.bytes + 255) & ~(size_t)255;
+    L.chunk = c.T > 128 ? ceil_div(c.T, 32) : 4;
+    L.ntask = append_ntasks(c.T, L.chunk);
+    L.nfill = std::min(ceil_div(c.n + k, nb) * nb, 256);
+    Carve cv(ws ? (char*)ws + o : nullptr);
+    L.mean = cv.take<double>((size_t)APPEND_MAXK * c.p);
+    L.var = cv.take<double>((size_t)APPEND_MAXK);
+    L.W = cv.take<double>((size_t)APPEND_MAXK * c.npad);
+    L.Rw = cv.take<double>((size_t)APPEND_MAXK * APPEND_MAXK);
+    L.cnt = cv.take<int>((size_t)c.T);
+    L.part = cv.take<double>((size_t)L.ntask * APPEND_MAXK * nb);
+    L.bytes = o + cv.off + 256;
+    return L;
+}
+
+template <int NB>
+static int gpr_posterior_append_impl(mfgp_handle_t h, int nlf, int n, int p, int d, int k, const void* cache,
+                                     size_t cache_bytes, const double* Xadd, int ldxa, const double* Yadd, int ldya,
+                                     void* ws, size_t ws_bytes, void* out_cache, size_t out_bytes, double* mean_add,
+                                     int ldm, int* info) {
+    const GprCache c = gpr_cache_layout(NB, nlf, n, p, d, cache);
+    const GprCache o = gpr_cache_layout(NB, nlf, n + k, p, d, out_cache);
+    const AppendLayout L = append_layout(NB, c, k, ws);
+    if (cache_bytes < c.bytes || out_bytes < o.bytes || ws_bytes < L.bytes) return MFGP_ERR_WORKSPACE;
+    hipStream_t s = h->stream;
+    double* mean = mean_add ? mean_add : L.mean;
+    const long ldmean = mean_add ? ldm : p;
+    PostArgs a = gpr_post_args(c, L.P, Xadd, ldxa, k, mean, ldmean, L.var, true);
+    a.swap = 1;   // the new rows sit below the cached ones: the cross block has the new row as its row argument
+    launch_post<NB>(a, 1, s);
+    AppendArgs g{};
+    g.LZ = c.LZ; g.ldr = c.ldr; g.X = c.X; g.theta = c.theta;
+    g.n = n; g.npad = c.npad; g.T = c.T;
+    g.p = p; g.ppad = c.ppad; g.D = d; g.nlf = nlf; g.G = c.G; g.k = k;
+    g.diag_add = nlf ? GRAPH_JITTER : 0.0;
+    g.Xadd = Xadd; g.ldxa = ldxa; g.Yadd = Yadd; g.ldya = ldya;
+    g.Am = L.P.Am; g.ldam = L.P.nspad;
+    g.mean = mean; g.ldm = ldmean;
+    g.W = L.W; g.Rw = L.Rw; g.cnt = L.cnt; g.part = L.part;
+    g.chunk = L.chunk; g.ntask = L.ntask; g.nfill = L.nfill;
+    g.LZo = o.LZ; g.ldro = o.ldr; g.npado = o.npad;
+    g.Xo = o.X; g.thetao = o.theta;
+    g.obase = (unsigned char*)out_cache;
+    const char* ob = (const char*)out_cache;
+    g.gap0[0] = (const char*)(o.X + (size_t)(n + k) * (d + 1)) - ob; g.gap1[0] = (const char*)o.theta - ob;
+    g.gap0[1] = (const char*)(o.theta + o.G) - ob;                   g.gap1[1] = (const char*)o.LZ - ob;
+    g.gap0[2] = (const char*)(o.LZ + (size_t)o.npad * o.ldr) - ob;   g.gap1[2] = (long)o.bytes;
+    g.info = info;
+    launch_append<NB>(g, s);
+    return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
+}
+
 // SVGP cache: [Z: m x (d + 1)][thetas: l x G][W: p x l][q_mu^T: l x Mpad, zero padded]
 //             [Lm^{-1}: l x Mpad x Mpad][C = Lq^T Lm^{-1}: l x Mpad x Mpad]
 struct SvgpCache {
@@ -348,6 +414,10 @@ static inline bool nlf_ok(int nlf) { return nlf >= 0 && nlf <= MFGP_MAX_LF; }
 static inline bool gpr_geometry_ok(int nlf, int n, int p) { return nlf_ok(nlf) && n >= 1 && p >= 1; }
 static inline bool design_geometry_ok(int nlf, int n, int p, int nref, int ncand) {
     return gpr_geometry_ok(nlf, n, p) && nref >= 0 && ncand >= 0 && (long)nref + ncand <= 0x7fffffffL - 4096;
+}
+
+static inline bool append_geometry_ok(int nlf, int n, int p, int k) {
+    return gpr_geometry_ok(nlf, n, p) && k >= 1 && k <= APPEND_MAXK && (long)n + k <= 0x7fffffffL - 4096;
 }
 
 }  // namespace mfgp
@@ -501,6 +571,27 @@ int mfgp_gpr_posterior_design_append(mfgp_handle_t h, int nlf, int n, int p, int
     if (!cache || !Xall || !ws || !pick || !E || ldx < d + 1 || ldE < nref + ncand) return MFGP_ERR_ARG;
     return TILE_CALL(h->nb, gpr_posterior_design_impl, h, nlf, n, p, d, cache, cache_bytes, Xall, ldx, nref, ncand,
                      nullptr, E, ldE, k, ws, ws_bytes, nullptr, 0, pick);
+}
+
+int mfgp_gpr_posterior_append_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int k, size_t* bytes) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (!append_geometry_ok(nlf, n, p, k) || !bytes) return MFGP_ERR_ARG;
+    *bytes = append_layout(h->nb, gpr_cache_layout(h->nb, nlf, n, p, d, nullptr), k, nullptr).bytes;
+    return MFGP_OK;
+}
+
+int mfgp_gpr_posterior_append(mfgp_handle_t h, int nlf, int n, int p, int d, int k, const void* cache,
+                              size_t cache_bytes, const double* Xadd, int ldxa, const double* Yadd, int ldya, void* ws,
+                              size_t ws_bytes, void* out_cache, size_t out_bytes, double* mean_add, int ldm,
+                              int* info) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (!append_geometry_ok(nlf, n, p, k) || !cache || !Xadd || !ws || !out_cache || !info || out_cache == cache ||
+        ldxa < d + 1 || (Yadd && ldya < p) || (mean_add && ldm < p))
+        return MFGP_ERR_ARG;
+    return TILE_CALL(h->nb, gpr_posterior_append_impl, h, nlf, n, p, d, k, cache, cache_bytes, Xadd, ldxa, Yadd, ldya,
+                     ws, ws_bytes, out_cache, out_bytes, mean_add, ldm, info);
 }
 
 int mfgp_svgp_posterior_size(mfgp_handle_t h, int m, int l, int p, int d, size_t* bytes) {

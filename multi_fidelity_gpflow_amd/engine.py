@@ -640,6 +640,22 @@ class Engine:
                                                         d + 1, nref, nall - nref, ptr(ws), ws.numel(), ptr(pick),
                                                         ptr(E), nall, k), "mfgp_gpr_posterior_design_append")
 
+    def gpr_posterior_append(self, nlf, shape, cache, Xadd, Yadd, out_cache):
+        """Fill `out_cache` (>= gpr_posterior_bytes of n + k rows) with the cache of [X ; Xadd], [Y ; Yadd] from
+        the factors in `cache` (Yadd None: the rows are observed at their own mean).  Returns the mean of
+        `cache` at Xadd [k, p] and info [1] (int32, device)."""
+        n, p, d = shape
+        k = Xadd.shape[0]
+        mean = torch.empty((k, p), dtype=torch.float64, device=self.device)
+        info = torch.empty((1,), dtype=torch.int32, device=self.device)
+        ws = self.workspace("post_append", self._size(self.lib.mfgp_gpr_posterior_append_workspace_size, nlf, n, p, d,
+                                                      k))
+        check(self.lib.mfgp_gpr_posterior_append(self.h, nlf, n, p, d, k, ptr(cache), cache.numel(), ptr(Xadd),
+                                                 Xadd.shape[1], ptr(Yadd), p, ptr(ws), ws.numel(), ptr(out_cache),
+                                                 out_cache.numel(), ptr(mean), p, ptr(info)),
+              "mfgp_gpr_posterior_append")
+        return mean, info
+
     def svgp_posterior_bytes(self, m, L, p, d) -> int:
         return self._size(self.lib.mfgp_svgp_posterior_size, m, L, p, d)
 

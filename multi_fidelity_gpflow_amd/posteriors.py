@@ -20,6 +20,10 @@ Simulation design: ``GPRPosterior.variance_reduction(Xcand, Xref, weights)`` sco
 the posterior variance it buys down over a reference set, and ``GPRPosterior.select`` picks a greedy batch
 by ``argmax(score / cost)``, both in closed form from the cached factors (``mfgp_gpr_posterior_design_score``
 / ``_append``: the reference x candidate covariance block is formed on chip, never in memory).
+
+New simulations: ``GPRPosterior.condition_on(Xadd, Yadd)`` returns the posterior of the stacked data at the
+snapshot's hyper-parameters from the cached factors (``mfgp_gpr_posterior_append``: a block append in
+O(N^2 k), no Gram, no factorization of K); ``fantasize(Xadd)`` conditions on rows that have no value yet.
 """
 from __future__ import annotations
 
@@ -82,6 +86,9 @@ class LeaveOutResult(NamedTuple):
 
 
 MAX_BATCH = 32   # picks of one greedy batch (include/mfgp.h mfgp_gpr_posterior_design_score: k <= 32)
+
+
+MAX_APPEND = 32  # rows of one condition_on call (include/mfgp.h mfgp_gpr_posterior_append: k <= 32)
 
 
 class DesignResult(NamedTuple):
@@ -334,16 +341,93 @@ class GPRPosterior(_Posterior):
     def __init__(self, model, nlf: int, theta_fn, precompute_cache):
         self._nlf = int(nlf)
         self._theta_fn = theta_fn
+        self._stacked = None   # a conditioned posterior's own (X, Y, theta) device tensors
+        self._theta = None     # the theta tensor of the last build
         super().__init__(model, precompute_cache)
 
+    def _data(self):
+        """(engine, X, Y) the cache stands for: the model's construction-time data (they cannot be
+        reassigned), or the stacked rows of a conditioned posterior."""
+        if self._stacked is None:
+            return self.model._device_data()
+        X, Y, _ = self._stacked
+        return Engine.get(X.device), X, Y
+
     def _build(self):
-        eng, X, Y = self.model._device_data()
-        theta = torch.tensor(self._theta_fn(), dtype=torch.float64, device=eng.device)
+        eng, X, Y = self._data()
+        if self._stacked is None:
+            theta = torch.tensor(self._theta_fn(), dtype=torch.float64, device=eng.device)
+        else:
+            theta = self._stacked[2]   # frozen: the rebuild of a conditioned posterior is exact at its snapshot
         n, p, d = X.shape[0], Y.shape[1], X.shape[1] - 1
         buf = self._cache_buffer(eng, eng.gpr_posterior_bytes(self._nlf, n, p, d))
         info = eng.gpr_posterior_build(self._nlf, X, Y, theta, buf)
         self._shape, self._nb = (n, p, d), eng.tile()
         self._commit(buf, info, "posterior")
+        self._theta = theta   # (after the commit: a TENSOR cache that keeps its contents keeps their theta)
+
+    def fused_predict_f(self, Xnew, full_cov: bool = False, full_output_cov: bool = False):
+        if self._stacked is not None:
+            raise NotImplementedError("fused_predict_f: a conditioned posterior's rows are not in the model; "
+                                      "use predict_f")
+        return super().fused_predict_f(Xnew, full_cov=full_cov, full_output_cov=full_output_cov)
+
+    def condition_on(self, Xadd, Yadd=None) -> "GPRPosterior":
+        """The posterior after k more simulations (1 <= k <= 32), at the snapshot's hyper-parameters: a NEW
+        posterior of ``vstack(X, Xadd)``, ``vstack(Y, Yadd)`` in that row order, from the cached factors by
+        a block append (mfgp_gpr_posterior_append: O(N^2 k), no Gram of X, no factorization of K).  Xadd
+        [k, D + 1] (fidelity in the last column), Yadd [k, P] (or [k] when P = 1); numpy, lists or device
+        tensors.  This posterior and its cache block are not written.  Everything that runs from a cache
+        runs on the result (predict_f, predict_f_vjp, leave_out, variance_reduction / select,
+        condition_on); it keeps the stacked data and the frozen theta, inherits the cache type, and its
+        ``update_cache()`` is the exact rebuild from the stacked data at the frozen theta (the way to shed
+        the rounding of many appends).  ``.model`` stays the original model, which does not hold the new
+        rows: ``fused_predict_f`` raises NotImplementedError.
+
+        ``Yadd=None`` (``fantasize``): the rows are observed at this posterior's own mean, so the mean is
+        unchanged and the variance is that of the refit: the exact look-ahead on runs not yet made.
+
+        ValueError before any device work: a wrong shape, k outside 1..32.  The call's one host read is
+        info: ValueError for a row whose fidelity is no source of the kernel, CholeskyError when the new
+        rows' conditional covariance is not positive definite (e.g. a NaN input); no posterior is returned.
+
+        Graph model: the cross block is the one a factorization of the stacked rows reads (the new row is
+        the row argument of the kernel's entry function), so the result is the refit's for any ``rho_LF``."""
+        self._need_cache("condition_on: a NOCACHE posterior has no cached factors to append to; use a TENSOR or "
+                         "VARIABLE cache")
+        n, p, d = self._shape
+        k = _design_rows(Xadd, d, "condition_on: Xadd")
+        if k < 1 or k > MAX_APPEND:
+            raise ValueError(f"condition_on: Xadd has {k} rows; 1..{MAX_APPEND} rows can be appended in one call")
+        if Yadd is not None:
+            shape = tuple(Yadd.shape) if isinstance(Yadd, torch.Tensor) else np.shape(Yadd)
+            if shape != (k, p) and not (p == 1 and shape == (k,)):
+                raise ValueError(f"condition_on: Yadd has shape {shape}, expected ({k}, {p})")
+        eng = self._engine()   # every ValueError of the arguments is raised above
+        Xa = to_dev(Xadd, eng.device)
+        Ya = None if Yadd is None else to_dev(Yadd, eng.device).reshape(k, p)
+        buf = torch.empty(int(eng.gpr_posterior_bytes(self._nlf, n + k, p, d)), dtype=torch.uint8, device=eng.device)
+        mean, info = eng.gpr_posterior_append(self._nlf, self._shape, self.cache, Xa, Ya, buf)
+        _, X, Y = self._data()
+        stacked = (torch.cat([X, Xa]), torch.cat([Y, mean if Ya is None else Ya]), self._theta)
+        bad = int(info.item())   # the one host read of a device word
+        if bad < 0:
+            raise ValueError(f"condition_on: row {-bad - 1} of Xadd has a fidelity that is no source of the kernel")
+        if bad > 0:
+            raise CholeskyError(f"condition_on: the conditional covariance of the new rows is not positive "
+                                f"definite (pivot {bad}); the input might not be valid.")
+        post = object.__new__(GPRPosterior)
+        post.model, post._nlf, post._theta_fn = self.model, self._nlf, self._theta_fn
+        post._precompute_cache = self._precompute_cache
+        post._stacked, post._theta = stacked, self._theta
+        post._shape, post._nb = (n + k, p, d), self._nb
+        post.cache, post._valid = buf, True
+        return post
+
+    def fantasize(self, Xadd) -> "GPRPosterior":
+        """``condition_on(Xadd)`` without values: the posterior after runs at Xadd whose results are not in
+        yet (same mean, the refit's variance)."""
+        return self.condition_on(Xadd, None)
 
     def predict_f(self, Xnew, full_cov: bool = False, full_output_cov: bool = False):
         """The model's predict_f at the snapshot (same shapes: mean [N*, P]; var [N*, P] or, with
@@ -409,7 +493,7 @@ class GPRPosterior(_Posterior):
         idx = torch.from_numpy(np.concatenate([offsets, rows, pos.astype(np.int32)])).to(eng.device)
         d_off, d_rows, d_pos = idx[:ng + 1], idx[ng + 1:ng + 1 + nr], idx[ng + 1 + nr:].long()
         resid, cov, logd, info = eng.gpr_posterior_leave_out(self._nlf, self._shape, self.cache, d_off, d_rows, gmax)
-        Y = self.model._device_data()[2]   # the construction-time targets (they cannot be reassigned)
+        Y = self._data()[2]
         mean = Y.index_select(0, d_rows) - resid
         var = cov.gather(1, d_pos[:, None]).expand(-1, p).contiguous()
         full = None
