@@ -720,6 +720,9 @@ __global__ __launch_bounds__(GT, 2) void k32_grad(F32Args a) {
         const float f1 = fi[r];
         const bool L1 = f1 == 0.0f, H1 = f1 == 1.0f;
         const float w = smem[r * (TB + 1) + c];
+        // s2 I sits on every training row, also one whose fidelity is neither 0 nor 1 (k32_gram):
+        // the noise term comes before the mask test, as in the fp64 k_grad
+        if (I == J && r == c && I * TB + r < a.n) gno += w;
         if (!((L1 || H1) && (L2 || H2))) continue;
         float df2[DT];
         float s2 = 0.0f, s2d = 0.0f;
@@ -738,7 +741,6 @@ __global__ __launch_bounds__(GT, 2) void k32_grad(F32Args a) {
         gvL += w * si * sj * eL;
         gvD += w * hi * hj * eD;
         grho += w * (hi * sj + si * hj) * kL;
-        if (I == J && r == c && I * TB + r < a.n) gno += w;
 #pragma unroll
         for (int d = 0; d < DT; ++d) {
             tl[d] = fmaf(cL, df2[d], tl[d]);

@@ -15,8 +15,10 @@ fp64 refinement step and the predictive mean two (mfgp_set_f32_refine; DESIGN.md
   n = 2300 vs oracle          1e-5 (2.2e-6 measured)                  1e-5 (2.8e-7; one step 1.7e-5)
   Synth vs f64                1.5e-4 (5.1e-5)                         1e-4 (1.4e-5; one step 3.9e-4)
 Properties that hold to rounding of the fp64 reductions at any size: additivity of the LML over
-output columns (one shared factorization), identical results with and without the lookahead
-schedule and for every panel width that tiles the same way."""
+output columns (one shared factorization), and bitwise identical results with and without the
+lookahead schedule, for every reserve, and for two panel widths that launch the same sequence
+(at T = 5, W = 5 and W = 9: one panel each; other widths contract the trailing update in other
+pieces and agree to rounding only).  tests/test_gpu_f32_edges.py checks those."""
 import numpy as np
 import pytest
 import torch
@@ -114,7 +116,10 @@ def test_f32_refined_value_and_mean_vs_oracle(eng):
 
 
 def test_f32_schedules_agree_bitwise(eng):
-    """Lookahead (side stream) vs one stream: the same kernels on the same data, so the same bits."""
+    """Lookahead (side stream) vs one stream: the same kernels on the same data, so the same bits.
+    Panels of 2 at T = 9, so the sweep forks (at the handle default of 6, k2 = 9 is not < T and
+    both schedules launch the same thing)."""
+    eng.set_f32_panel(2)
     X, Y, _, _ = synthetic_multifidelity(900, 200, 10, 40, 8, seed=2)
     m = _model(X, Y)
     res = []
