@@ -229,6 +229,34 @@ int mfgp_potrf_inv_workspace_size(mfgp_handle_t h, int n, int batch, size_t* byt
 int mfgp_potrf_inv(mfgp_handle_t h, int n, int batch, const double* A, int lda, long sA, void* ws, size_t ws_bytes,
                    double* Linv, int ldl, long sL, double* ldiag, int* info);
 
+/* Joint Gaussian draws from a batch of dense covariances: with L_b = chol(cov_b + jitter I) (lower),
+ *   out(b, s, i, c) = mean(b, i, c) + sum_{j <= i} L_b[i][j] eps(b, s, j, c),
+ * b < batch, s < nsamp, i < n, c < ncol.
+ *   cov    cov_b is [n][ldc] at b * sC (ldc >= n).  Only its lower triangle is read (as TF's cholesky
+ *          reads it) and it is never written; jitter is added to the diagonal as the tiles are loaded.
+ *   eps    the standard-normal input, and out: element (b, s, i, c) at b * bs + s * ss + i * rs + c.
+ *          eps must not alias out.
+ *   mean   element (b, i, c) at b * mean_bs + i * mean_rs + c.
+ *   info   [batch]: 0, or the 1-based row of the first non-positive or non-finite pivot of entry b; that
+ *          entry's output is then unspecified, the other entries are unaffected.
+ * One factor serves all ncol columns of its batch entry.  GPR (one [N*, N*] block for the P outputs):
+ * batch = 1, ncol = P, rs = P, ss = N* P.  SVGP ([P, N*, N*]): batch = P, ncol = 1, bs = 1, rs = P,
+ * ss = N* P, mean_bs = 1, mean_rs = P -- [N*, P] is read and [S, N*, P] written with no transposed copy.
+ * 32 x 32 tiles whatever the handle's tile size: a left-looking tile Cholesky that keeps L (one launch
+ * per tile column, launch boundaries the only ordering between workgroups), then one launch for the
+ * triangular product L eps with the mean added in its epilogue (upper tiles are never touched).
+ * ceil(n / 32) + 1 launches.  Fixed-order sums and no floating-point atomics (the same inputs give the
+ * same bits); nothing is allocated, no synchronisation, no host read of a device word.  n = 0 or
+ * nsamp = 0: a no-op (MFGP_OK; decided before the pointers are looked at, nothing is written).  A negative
+ * count, batch < 1 (or > 65535), ncol < 1, ldc < n or a null pointer: MFGP_ERR_ARG; a workspace smaller than
+ * mfgp_mvn_sample_workspace_size reports: MFGP_ERR_WORKSPACE; both before any device work.
+ * Replaces: gpflow GPModel.predict_f_samples (models/model.py) and conditionals/util.py sample_mvn
+ * (tf.linalg.cholesky(cov + default_jitter() I) @ eps + mean), inherited by every model of the reference. */
+int mfgp_mvn_sample_workspace_size(mfgp_handle_t h, int n, int batch, size_t* bytes);
+int mfgp_mvn_sample(mfgp_handle_t h, int n, int batch, int nsamp, int ncol, const double* cov, int ldc, long sC,
+                    double jitter, const double* mean, long mean_rs, long mean_bs, const double* eps, double* out,
+                    long rs, long ss, long bs, void* ws, size_t ws_bytes, int* info /* [batch] */);
+
 /* SVGP ELBO value (GPflow SVGP.elbo, whiten=True, Gaussian likelihood) for the
  * latent LinearCoregionalization model (mfgpflow/linear_svgp.py:64-203) and the
  * SingleBinSVGP (SeparateIndependent, mfgpflow/singlebin_svgp.py:13-97, W = I):

@@ -58,6 +58,8 @@ SIGNATURES = {
     "mfgp_gpr_predict_cov": [_p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _sz, _p, _i, _p, _p, _i, _p],
     "mfgp_potrf_inv_workspace_size": [_p, _i, _i, C.POINTER(_sz)],
     "mfgp_potrf_inv": [_p, _i, _i, _p, _i, _l, _p, _sz, _p, _i, _l, _p, _p],
+    "mfgp_mvn_sample_workspace_size": [_p, _i, _i, C.POINTER(_sz)],
+    "mfgp_mvn_sample": [_p, _i, _i, _i, _i, _p, _i, _l, _d, _p, _l, _l, _p, _p, _l, _l, _l, _p, _sz, _p],
     "mfgp_svgp_workspace_size": [_p, _i, _i, _i, _i, _i, C.POINTER(_sz)],
     "mfgp_svgp_elbo": [_p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _d, _d, _d, _p, _sz, _p,
                        _p, _p, _p],

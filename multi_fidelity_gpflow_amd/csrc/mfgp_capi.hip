@@ -1122,6 +1122,32 @@ int mfgp_potrf_inv(mfgp_handle_t h, int n, int batch, const double* A, int lda, 
     return TILE_CALL(h->nb, potrf_inv_impl, h, n, batch, A, lda, sA, ws, ws_bytes, Linv, ldl, sL, ldiag, info);
 }
 
+int mfgp_mvn_sample_workspace_size(mfgp_handle_t h, int n, int batch, size_t* bytes) {
+    CHECK_H(h);
+    if (n < 0 || batch < 1 || batch > 65535 || !bytes) return MFGP_ERR_ARG;
+    *bytes = mvn_sample_ws_bytes(n, batch);
+    return MFGP_OK;
+}
+
+int mfgp_mvn_sample(mfgp_handle_t h, int n, int batch, int nsamp, int ncol, const double* cov, int ldc, long sC,
+                    double jitter, const double* mean, long mean_rs, long mean_bs, const double* eps, double* out,
+                    long rs, long ss, long bs, void* ws, size_t ws_bytes, int* info) {
+    CHECK_H(h);
+    if (n < 0 || nsamp < 0 || batch < 1 || batch > 65535 || ncol < 1 || ldc < n) return MFGP_ERR_ARG;
+    if ((long)nsamp * ncol > 0x7fffffffL) return MFGP_ERR_ARG;
+    if (n == 0 || nsamp == 0) return MFGP_OK;
+    if (!cov || !mean || !eps || !out || !ws || !info || eps == out) return MFGP_ERR_ARG;
+    if (ws_bytes < mvn_sample_ws_bytes(n, batch)) return MFGP_ERR_WORKSPACE;
+    SampleArgs a{};
+    a.cov = cov; a.ldc = ldc; a.sC = sC; a.jitter = jitter;
+    a.mean = mean; a.mean_rs = mean_rs; a.mean_bs = mean_bs;
+    a.eps = eps; a.out = out; a.rs = rs; a.ss = ss; a.bs = bs;
+    a.info = info;
+    a.n = n; a.batch = batch; a.nsamp = nsamp; a.ncol = ncol;
+    launch_mvn_sample(a, ws, h->stream);
+    return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
+}
+
 int mfgp_svgp_workspace_size(mfgp_handle_t h, int n, int m, int l, int p, int d, size_t* bytes) {
     CHECK_H(h);
     CHECK_D(d);

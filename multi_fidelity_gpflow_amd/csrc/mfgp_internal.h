@@ -558,4 +558,19 @@ __global__ void k_theta_from_u(const double* u, double* theta, int G, int noise_
 __global__ void k_kdiag(const double* X, long ldx, int n, int D, const double* theta, double* out, int nlf);
 __global__ void k_selftest_mfma(double* out);
 
+// mfgp_mvn_sample (mfgp_sample.hip): out(b, s, i, c) = mean(b, i, c) + sum_{j <= i} L_b[i][j] eps(b, s, j, c),
+// L_b = chol(cov_b + jitter I); the addressing is include/mfgp.h's.
+struct SampleArgs {
+    const double* cov; long ldc, sC;
+    double jitter;
+    const double* mean; long mean_rs, mean_bs;
+    const double* eps;
+    double* out; long rs, ss, bs;
+    double* Lw; long ldl, sL;   // the factor's 32-tiles in the workspace (set by launch_mvn_sample)
+    int* info;
+    int n, batch, nsamp, ncol;
+};
+size_t mvn_sample_ws_bytes(int n, int batch);
+void launch_mvn_sample(SampleArgs a, void* ws, hipStream_t s);
+
 }  // namespace mfgp

@@ -395,6 +395,33 @@ class Engine:
             return Linv[0], ld[0], info
         return Linv, ld, info
 
+    def mvn_sample(self, cov: torch.Tensor, mean: torch.Tensor, eps: torch.Tensor, ncol: int, jitter: float = 1e-6):
+        """Joint draws (include/mfgp.h mfgp_mvn_sample): cov [B, n, n] (any row / batch stride, unit
+        inner stride; only the lower triangles are read), mean [n, B * ncol], eps [S, n, B * ncol] ->
+        (out [S, n, B * ncol], info [B]), out[s, :, b * ncol + c] = mean[:, b * ncol + c] +
+        chol(cov[b] + jitter I) @ eps[s, :, b * ncol + c].  One factor per batch entry serves its ncol
+        columns: GPR is B = 1, ncol = P; SVGP is B = P, ncol = 1.  No host read of a device word."""
+        if cov.dim() != 3 or cov.shape[1] != cov.shape[2]:
+            raise ValueError(f"mvn_sample: cov has shape {tuple(cov.shape)}, expected [B, n, n]")
+        b, n, _ = cov.shape
+        w = b * int(ncol)
+        if mean.shape != (n, w) or eps.dim() != 3 or tuple(eps.shape[1:]) != (n, w):
+            raise ValueError(f"mvn_sample: mean {tuple(mean.shape)} / eps {tuple(eps.shape)} do not match "
+                             f"[{n}, {w}] / [S, {n}, {w}]")
+        if n > 1 and (cov.stride(2) != 1 or cov.stride(1) < n):
+            cov = cov.contiguous()
+        ldc = max(cov.stride(1), n, 1)
+        sC = cov.stride(0) if b > 1 else 0
+        mean, eps = mean.contiguous(), eps.contiguous()
+        ns = eps.shape[0]
+        out = torch.empty_like(eps)
+        info = torch.zeros((b,), dtype=torch.int32, device=self.device)
+        ws = self.workspace("mvn_sample", self._size(self.lib.mfgp_mvn_sample_workspace_size, n, b))
+        check(self.lib.mfgp_mvn_sample(self.h, n, b, ns, int(ncol), ptr(cov), ldc, sC, float(jitter), ptr(mean), w,
+                                       int(ncol), ptr(eps), ptr(out), w, n * w, int(ncol), ptr(ws), ws.numel(),
+                                       ptr(info)), "mfgp_mvn_sample")
+        return out, info
+
     @staticmethod
     def _check_yunc(Yunc, Y, n, p):
         """The heteroscedastic entry points' Yunc: fp64 [n, >= p] on Y's device, unit inner stride."""

@@ -31,7 +31,7 @@ from .engine import AdamState, Engine, resolve_dtype, theta_size, to_dev
 from .kernels import LinearMultiFidelityKernel
 from .params import (Module, Parameter, as_result, gather_entries, positive, scatter_entries, set_trainable,
                      tie_entries)
-from .posteriors import GPRPosterior, PrecomputeCacheType
+from .posteriors import DEFAULT_SAMPLE_JITTER, GPRPosterior, PrecomputeCacheType, draw_f_samples
 from .session import (CholeskyError, _Session, _StepRunner, _retire_graphs, _retired_graphs,  # noqa: F401
                       check_outcome, new_stream, release_retired_graphs)
 
@@ -228,6 +228,28 @@ class MultiFidelityGPModel(Module):
                                       "full_cov=False and full_output_cov=False")
         mean, var = self.predict_f(Xnew)
         return mean, as_result(var + float(self.likelihood.variance.numpy()))
+
+    def predict_f_samples(self, Xnew, num_samples=None, full_cov: bool = True, full_output_cov: bool = False, *,
+                          eps=None, generator=None, jitter: float = DEFAULT_SAMPLE_JITTER):
+        """GPflow GPModel.predict_f_samples at the current parameters: [S, N*, P] joint draws (one draw
+        [N*, P] with num_samples=None); arguments, errors and the detached result as
+        posteriors.GPRPosterior.predict_f_samples.  The one [N*, N*] block of predict_f(full_cov=True) is
+        factored once for all P outputs (mfgp_mvn_sample), never tiled.  fp64 only."""
+        if self.dtype != torch.float64:
+            raise NotImplementedError("predict_f_samples(): the float32 path has no joint draws; use a float64 "
+                                      "model")
+
+        def inputs():
+            eng = Engine.get()
+            return eng, to_dev(Xnew, eng.device)
+
+        def joint(eng, Xs):
+            _, X, Y = self._device_data()
+            theta = torch.tensor(self._theta_map().theta(), dtype=torch.float64, device=eng.device)
+            mean, _, cov, info = eng.gpr_predict_cov(0, X, Y, Xs, theta)
+            return mean, cov[None], Y.shape[1], info
+        return draw_f_samples(self.num_output_dims, inputs, self.predict_f, joint, Xnew, num_samples, full_cov,
+                              full_output_cov, eps, generator, jitter)
 
     def posterior(self, precompute_cache=PrecomputeCacheType.TENSOR):
         """GPflow GPR.posterior(): a frozen snapshot of the parameters and data whose predict_f

@@ -24,6 +24,12 @@ by ``argmax(score / cost)``, both in closed form from the cached factors (``mfgp
 New simulations: ``GPRPosterior.condition_on(Xadd, Yadd)`` returns the posterior of the stacked data at the
 snapshot's hyper-parameters from the cached factors (``mfgp_gpr_posterior_append``: a block append in
 O(N^2 k), no Gram, no factorization of K); ``fantasize(Xadd)`` conditions on rows that have no value yet.
+
+Joint draws: ``predict_f_samples(Xnew, num_samples)`` is GPflow's ``sample_mvn`` on the device
+(``mfgp_mvn_sample``: a tile Cholesky of the predictive covariance that keeps L, then ``mean + L eps`` on
+the matrix core).  A GPR posterior factors its one [N*, N*] block once for all P outputs; an SVGP posterior
+factors the snapshot's [P, N*, N*].  ``eps=`` passes the standard-normal input (a deterministic call);
+the four models have the same method at their current parameters.
 """
 from __future__ import annotations
 
@@ -70,6 +76,91 @@ def _upstream(g, shape, device, what):
     if tuple(g.shape) != tuple(shape):
         raise ValueError(f"predict_f_vjp: {what} has shape {tuple(g.shape)}, expected {tuple(shape)}")
     return g
+
+
+DEFAULT_SAMPLE_JITTER = 1e-6   # gpflow.default_jitter(), what sample_mvn adds before its Cholesky
+
+
+def sample_plan(what, Xnew, p, num_samples, full_cov, full_output_cov, eps, jitter):
+    """The argument checks of predict_f_samples, all on the host before any device work:
+    ``(S, N*)`` with S the number of draws computed (1 for ``num_samples=None``).  NotImplementedError
+    for the output-covariance forms, ValueError for a bad ``num_samples`` / ``eps`` shape / ``jitter``."""
+    if full_cov and full_output_cov:
+        raise NotImplementedError(f"{what}: the combination of both full_cov and full_output_cov is not "
+                                  "permitted.")
+    if full_output_cov:
+        raise NotImplementedError(f"{what}(full_output_cov=True): draws from the [N*, P, P] output covariance "
+                                  "are not built; use full_cov=True or the marginal form")
+    if num_samples is not None:
+        if isinstance(num_samples, bool) or not isinstance(num_samples, (int, np.integer)):
+            raise ValueError(f"{what}: num_samples must be an integer >= 1 or None, got {num_samples!r}")
+        if num_samples < 1:
+            raise ValueError(f"{what}: num_samples must be >= 1, got {num_samples}")
+    if isinstance(jitter, bool) or not isinstance(jitter, (int, float, np.integer, np.floating)) or not jitter >= 0:
+        raise ValueError(f"{what}: jitter must be a number >= 0, got {jitter!r}")
+    shape = tuple(Xnew.shape) if isinstance(Xnew, torch.Tensor) else np.shape(Xnew)
+    if len(shape) != 2:
+        raise ValueError(f"{what}: Xnew has shape {shape}, expected [N*, D + 1]")
+    ns = int(shape[0])
+    S = 1 if num_samples is None else int(num_samples)
+    if eps is not None:
+        eshape = tuple(eps.shape) if isinstance(eps, torch.Tensor) else np.shape(eps)
+        if num_samples is None:
+            if eshape != (ns, p):
+                raise ValueError(f"{what}: eps has shape {eshape}, expected ({ns}, {p}) with num_samples=None")
+        elif len(eshape) != 3 or eshape[1:] != (ns, p):
+            raise ValueError(f"{what}: eps has shape {eshape}, expected ({S}, {ns}, {p})")
+        elif eshape[0] != S:
+            raise ValueError(f"{what}: eps holds {eshape[0]} draws, num_samples is {S}")
+    return S, ns
+
+
+def sample_eps(eng: Engine, eps, S, ns, p, generator):
+    """The standard-normal input [S, N*, P] on the engine's device: the caller's, or torch.randn."""
+    if eps is None:
+        return torch.randn((S, ns, p), dtype=torch.float64, device=eng.device, generator=generator)
+    return to_dev(eps, eng.device).reshape(S, ns, p)
+
+
+def sample_marginal(mean, var, eps, squeeze):
+    """sample_mvn(full_cov=False): mean + sqrt(var) eps (no jitter, no clamp of var)."""
+    out = mean.as_subclass(torch.Tensor)[None] + torch.sqrt(var.as_subclass(torch.Tensor))[None] * eps
+    return as_result(out[0] if squeeze else out)
+
+
+def sample_joint(eng: Engine, what, mean, cov, eps, ncol, jitter, squeeze, pre=None):
+    """sample_mvn(full_cov=True) on the device (Engine.mvn_sample): cov [B, N*, N*], B * ncol = P.  The
+    call's one host read is info, after everything is enqueued (`pre`: the info words of the call that
+    produced cov, read with it)."""
+    out, info = eng.mvn_sample(cov, mean, eps, ncol, jitter)
+    nb = info.shape[0]
+    bad = (info if pre is None else torch.cat([info, pre.reshape(-1)])).cpu().numpy()
+    if np.any(bad[nb:] != 0):
+        err = info_error(int(bad[nb:][np.flatnonzero(bad[nb:])[0]]), what)
+        raise err if pre.numel() == 1 else CholeskyError(f"{what}: Cholesky of K_uu was not successful")
+    bad = bad[:nb]
+    if np.any(bad != 0):
+        b = int(np.flatnonzero(bad)[0])
+        where = f" of output {b}" if cov.shape[0] > 1 else ""
+        raise CholeskyError(f"{what}: Cholesky decomposition of the predictive covariance{where} was not "
+                            f"successful (non-positive pivot at row {int(bad[b])}); the input might not be valid.")
+    return as_result(out[0] if squeeze else out)
+
+
+def draw_f_samples(p, inputs, marginal, joint, Xnew, num_samples, full_cov, full_output_cov, eps, generator, jitter):
+    """predict_f_samples of a posterior or a model with P = p outputs.  ``inputs() -> (engine, Xnew on the
+    device, detached)`` is called after the argument checks; ``marginal(Xs) -> (mean, var)`` is its marginal
+    predict_f; ``joint(engine, Xs) -> (mean [N*, P], cov [B, N*, N*], ncol, info words of that call or
+    None)`` its covariance entry point with B * ncol = P."""
+    what = "predict_f_samples"
+    S, ns = sample_plan(what, Xnew, p, num_samples, full_cov, full_output_cov, eps, jitter)
+    eng, Xs = inputs()   # every ValueError of the arguments is raised above
+    e = sample_eps(eng, eps, S, ns, p, generator)
+    if not full_cov:
+        mean, var = marginal(Xs)
+        return sample_marginal(mean, var, e, num_samples is None)
+    mean, cov, ncol, pre = joint(eng, Xs)
+    return sample_joint(eng, what, mean, cov, e, ncol, jitter, num_samples is None, pre)
 
 
 MAX_GROUP = 32   # rows of one left-out group (include/mfgp.h mfgp_gpr_posterior_leave_out: gmax <= 32)
@@ -296,6 +387,36 @@ class _Posterior:
         mean, var, gX = self._predict(self.cache, Xnew, grad=(grad_mean, grad_var))
         return as_result(mean), as_result(var), as_result(gX)
 
+    def predict_f_samples(self, Xnew, num_samples=None, full_cov: bool = True, full_output_cov: bool = False, *,
+                          eps=None, generator=None, jitter: float = DEFAULT_SAMPLE_JITTER):
+        """GPflow ``GPModel.predict_f_samples`` at the snapshot: joint draws of f(Xnew), [S, N*, P], or one
+        draw [N*, P] with ``num_samples=None``.
+
+        ``full_cov=True``: ``sample[s, :, p] = mean[:, p] + cholesky(cov_p + jitter I) @ eps[s, :, p]``
+        (``sample_mvn``; the lower factor of the lower triangle, ``jitter = default_jitter() = 1e-6``),
+        factored and multiplied on the device by mfgp_mvn_sample: no [P, N*, N*] copy of a GPR's one block,
+        no rocSOLVER call.  ``full_cov=False``: ``mean + sqrt(var) * eps`` on the marginal predict_f (no
+        jitter, no clamp of var).  ``full_output_cov=True`` raises NotImplementedError (with ``full_cov``
+        as GPflow does; alone because draws from the [N*, P, P] form are not built).
+
+        ``eps`` is the standard-normal input, [S, N*, P] ([N*, P] with ``num_samples=None``; numpy, list or
+        device tensor): a given ``eps`` makes the call deterministic.  ``None``: ``torch.randn`` on the
+        engine's device with ``generator``.  ValueError before any device work for a wrong ``eps`` shape,
+        a ``num_samples`` that is no integer >= 1 or disagrees with ``eps``, ``jitter < 0``.  The call's
+        one host read is the factorization's info, after everything is enqueued: CholeskyError with the
+        pivot (SVGP: and the output) when a covariance is not positive definite, e.g. a NaN input row.
+
+        The samples carry no autograd history: an Xnew with ``requires_grad`` returns detached samples.
+        A NOCACHE posterior delegates to the model (its current parameters)."""
+        if self._precompute_cache is PrecomputeCacheType.NOCACHE:
+            return self.model.predict_f_samples(Xnew, num_samples, full_cov, full_output_cov, eps=eps,
+                                                generator=generator, jitter=jitter)
+        def inputs():
+            eng = self._engine()
+            return eng, to_dev(Xnew, eng.device)
+        return draw_f_samples(self._num_outputs(), inputs, self.predict_f, self._joint, Xnew, num_samples, full_cov,
+                              full_output_cov, eps, generator, jitter)
+
     def _check_vjp(self):
         pass
 
@@ -464,6 +585,14 @@ class GPRPosterior(_Posterior):
             return mean, third[None].expand(p, -1, -1).contiguous(), None
         return mean, var[:, None].expand(-1, p).contiguous(), third
 
+    def _num_outputs(self) -> int:
+        return self._shape[1]
+
+    def _joint(self, eng, Xs):
+        """(mean [N*, P], the ONE [1, N*, N*] block, ncol = P): never tiled over P, factored once."""
+        mean, _, cov = eng.gpr_posterior_predict(self._nlf, self._shape, self.cache, Xs, True)
+        return mean, cov[None], self._shape[1], None
+
     def leave_out(self, groups=None, full_cov: bool = False) -> LeaveOutResult:
         """Leave-group-out cross-validation at the snapshot's hyper-parameters: for every group of
         training rows, what a model built without those rows predicts for them (``predict_f`` of that
@@ -630,6 +759,15 @@ class SVGPPosterior(_Posterior):
             return as_result(f_mu), as_result(f_cov)
         f_mu, f_var, _ = self._predict(self.cache, Xnew)
         return as_result(f_mu), as_result(f_var)
+
+    def _num_outputs(self) -> int:
+        return self._shape[2]
+
+    def _joint(self, eng, Xs):
+        """(mean [N*, P], cov [P, N*, N*] of the snapshot, ncol = 1): one factor per output."""
+        Z, thetas, q_mu, q_sqrt, W = self._state
+        mean, cov, kuu = eng.svgp_predict_cov(1, Xs, Z, thetas, q_mu, q_sqrt, W, self._shape[2], self._jitter)
+        return mean, cov, 1, kuu
 
     def _predict(self, cache, Xnew, grad=None):
         """The marginal predict_f on `cache`: (f_mu, f_var, None); with grad = (grad_mean, grad_var) the VJP

@@ -28,7 +28,7 @@ import torch
 from .engine import Engine, theta_size, to_dev
 from .kernels import LinearCoregionalization, LinearMultiFidelityKernel, SeparateIndependent
 from .models import CholeskyError, Gaussian, HeteroscedasticGaussian, MaskedGaussian
-from .posteriors import PrecomputeCacheType, SVGPPosterior
+from .posteriors import DEFAULT_SAMPLE_JITTER, PrecomputeCacheType, SVGPPosterior, draw_f_samples
 from .params import (Module, Parameter, Softplus, as_result, gather_entries, multiple_assign, parameter_dict,
                      scatter_entries, tie_entries)
 from .session import _PackedAdam, _Session, check_outcome, span_from_tie
@@ -200,6 +200,23 @@ class _SVGPBase(Module):
         if self._masked():
             return mean, as_result(var + to_dev(self._noise_vector(), var.device)[None, :])
         return mean, as_result(var + self._noise())
+
+    def predict_f_samples(self, Xnew, num_samples=None, full_cov: bool = True, full_output_cov: bool = False, *,
+                          eps=None, generator=None, jitter: float = DEFAULT_SAMPLE_JITTER):
+        """GPflow GPModel.predict_f_samples at the current parameters: [S, N*, P] joint draws (one draw
+        [N*, P] with num_samples=None); arguments, errors and the detached result as
+        posteriors.SVGPPosterior.predict_f_samples.  The [P, N*, N*] of predict_f(full_cov=True) is factored
+        per output and multiplied on the device (mfgp_mvn_sample)."""
+        def inputs():
+            eng = Engine.get()
+            return eng, to_dev(Xnew, eng.device)
+
+        def joint(eng, Xs):
+            _, Z, thetas, q_mu, q_sqrt, W = self._dev_state()
+            mean, cov, kuu = eng.svgp_predict_cov(1, Xs, Z, thetas, q_mu, q_sqrt, W, self.num_outputs, DEFAULT_JITTER)
+            return mean, cov, 1, kuu
+        return draw_f_samples(int(self.num_outputs), inputs, self.predict_f, joint, Xnew, num_samples, full_cov,
+                              full_output_cov, eps, generator, jitter)
 
     def posterior(self, precompute_cache=PrecomputeCacheType.TENSOR):
         """GPflow SVGP.posterior(): a frozen snapshot of Z, the kernels, q(u) and W whose marginal
