@@ -1,10 +1,16 @@
-// What the host translation units of the C ABI (mfgp_capi.hip, mfgp_posterior_capi.hip) share.  Host-only: no
-// device translation unit includes it.  gpr_layout, gpr_factor and copy_block are defined in mfgp_capi.hip.
+// What the host translation units of the C ABI share.  Host-only: no device translation unit includes it.
+//   mfgp_capi.hip            the handle and its settings, Gram / kdiag, potrf_inv, copy_block, mvn_sample,
+//                            adam_packed, the SVGP entries
+//   mfgp_fence.hip           the device-wide flow fence (mfgp_fence.h) and mfgp_flow_fence
+//   mfgp_gpr_capi.hip        fp64 GPR / graph-kernel training and predict: gpr_layout, gpr_factor
+//   mfgp_f32_capi.hip        the fp32 path, the fp32 settings and the dtype-generic *_ex entries
+//   mfgp_posterior_capi.hip  the cached posterior
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/mfgp.h"
 #include "mfgp_internal.h"
+#include "mfgp_device.h"   // theta_size, MFGP_MAX_LF
 
 struct mfgp_handle_s {
     int device;
@@ -62,13 +68,90 @@ struct GprLayout {
     int gchunk;         // k_grad's task chunk (m-tiles per task)
     size_t bytes;
 };
-GprLayout gpr_layout(int nb, int n, int p, int d, void* ws, int grad_chunk, int nlf = 0, int flow_wgs = 0,
-                     int flow_min_t = 0);
+
+// One GPR call, filled once by its C-ABI entry and taken by const reference by every driver and builder:
+// a driver's signature names everything it reads, and nothing else does.  T: the scalar of X and Y
+// (fp64, or float on the fp32 path); theta is fp64 and read-only here -- the Adam entries' writable
+// theta travels in FinArgs::theta (adam_fin) alone.  A size query fills n, p, d, nlf only.
+template <class T>
+struct GprProblemT {
+    int n, p, d, nlf;         // nlf: 0 the linear multi-fidelity kernel, m >= 1 the graph kernel
+    const T* X; int ldx;
+    const T* Y; int ldy;
+    const double* theta;
+    void* ws; size_t ws_bytes;
+    int* info;
+};
+using GprProblem = GprProblemT<double>;
+template <class T>
+struct GprPredictIOT {
+    int nstar;
+    const T* Xs; int ldxs;
+    T* mean; int ldm;
+    T* var;
+    T* cov; int ldc;          // cov == nullptr: no covariance block
+};
+using GprPredictIO = GprPredictIOT<double>;
+
+// The argument checks of the GPR entries, before any device work, in the order the return codes of a
+// call that is wrong in several ways depend on: handle, d (MFGP_ERR_DIM), nlf in lf_min..MFGP_MAX_LF,
+// sizes, then rest_ok (the entry's own pointers and leading dimensions).
+static inline int gpr_check_dims(mfgp_handle_t h, int n, int p, int d, int nlf, int lf_min, bool rest_ok) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nlf < lf_min || nlf > MFGP_MAX_LF) return MFGP_ERR_ARG;
+    return n < 1 || p < 1 || !rest_ok ? MFGP_ERR_ARG : MFGP_OK;
+}
+template <class T>
+static int gpr_check(mfgp_handle_t h, const GprProblemT<T>& P, int lf_min, bool rest_ok) {
+    return gpr_check_dims(h, P.n, P.p, P.d, P.nlf, lf_min, P.X && P.Y && P.theta && P.ws && P.info && rest_ok);
+}
+// a predict entry's second check, behind its nstar == 0 return
+template <class T>
+static bool gpr_predict_io_ok(const GprPredictIOT<T>& io, bool want_cov) {
+    return io.Xs && io.mean && io.var && (!want_cov || (io.cov && io.ldc >= io.nstar));
+}
+
+// Below this many 32-tiles the launch-per-step Cholesky is faster than the persistent flow (one
+// 256-workgroup launch costs more than a few short step launches): fp64 value+grad evaluation,
+// flow vs steps (tools/flow_threshold.py): T = 2: 67.5 vs 56.8 us, T = 5: 83.2 vs 79.7, T = 7:
+// 95.3 vs 96.2, T = 9: 106.2 vs 110.6, T = 24: 195.9 vs 247.1.
+constexpr int FLOW_MIN_TILES = 8;
+
+// What of the handle's schedule a layout depends on; no_flow: the launch-per-step factorization whatever
+// the handle says (predict, the posterior build).
+struct GprSched { int grad_chunk, flow_wgs, flow_min_t; };
+static inline GprSched gpr_sched(mfgp_handle_t h) { return {h->grad_chunk, h->flow_wgs, h->flow_min_t}; }
+static inline GprSched gpr_sched_no_flow(mfgp_handle_t h) { return {h->grad_chunk, 0, 0}; }
+// reads n, p, d, nlf and ws of P (ws == nullptr only counts)
+GprLayout gpr_layout(int nb, const GprProblem& P, const GprSched& sc);
 
 // The LML-layout Gram and the launch-per-step factorization on L (gram_lml_and_factor at tile size nb):
 // L.Xo then holds [L^{-1} | Z].
-void gpr_factor(int nb, hipStream_t s, const GprLayout& L, int n, int p, int d, const double* X, int ldx,
-                const double* Y, int ldy, const double* theta, int* info, int nlf);
+void gpr_factor(int nb, hipStream_t s, const GprLayout& L, const GprProblem& P);
+
+// The evaluation part of k_reduce_items' / k_gpr_tiny's argument block: the problem, what to write, and
+// the Adam part (adam_fin) when the call is an Adam step.  The caller adds where its partial sums lie.
+template <class T>
+static FinArgs fin_eval(const GprProblemT<T>& P, int G, int want_grad, double* out, const FinArgs* adam) {
+    FinArgs f{};
+    if (adam) f = *adam;
+    f.info = P.info; f.P = P.p; f.D = P.d; f.want_grad = want_grad; f.out = out; f.n = P.n;
+    f.adam = adam != nullptr;
+    f.G = G;
+    return f;
+}
+// The Adam part from the C arguments of an Adam entry.  The one place FinArgs::theta is set: the step
+// refreshes the constrained theta the evaluation reads through the descriptor's const pointer.
+static inline FinArgs adam_fin(int d, double* theta, double* u, double* m, double* v, const unsigned char* trainable,
+                               const int* tie, int* step, double lr, double b1, double b2, double eps,
+                               double* loss_hist) {
+    FinArgs f{};
+    f.theta = theta; f.u = u; f.m = m; f.v = v; f.trainable = trainable; f.tie = tie; f.step = step;
+    f.lr = lr; f.b1 = b1; f.b2 = b2; f.eps = eps; f.loss_hist = loss_hist;
+    f.noise_index = theta_size(d) - 1;
+    return f;
+}
 
 // dst[r][c] = src[r][c] over rows x cols (k_copy_block)
 void copy_block(hipStream_t s, const double* src, long lds, double* dst, long ldd, int rows, int cols);

@@ -1,7 +1,7 @@
 // C-ABI entry points of the cached posterior (include/mfgp.h, mfgp_gpr_posterior_size through
 // mfgp_svgp_posterior_predict_vjp): the cache and workspace layouts, the argument blocks and the launch
 // sequences of mfgp_posterior.hip / mfgp_leave_out.hip / mfgp_design.hip / mfgp_append.hip.  Host-side
-// orchestration only, as mfgp_capi.hip: no allocation, no synchronisation.
+// orchestration only, as the other *_capi.hip files: no allocation, no synchronisation.
 #include <algorithm>
 
 #include "mfgp_device.h"
@@ -134,16 +134,14 @@ static PostArgs gpr_post_args(const GprCache& c, const PostLayout& P, const doub
     return a;
 }
 
-static int gpr_posterior_build_impl(mfgp_handle_t h, int nlf, int n, int p, int d, const double* X, int ldx,
-                                    const double* Y, int ldy, const double* theta, void* ws, size_t ws_bytes,
-                                    void* cache, size_t cache_bytes, int* info) {
-    const GprLayout L = gpr_layout(h->nb, n, p, d, ws, h->grad_chunk, nlf);
-    const GprCache c = gpr_cache_layout(h->nb, nlf, n, p, d, cache);
-    if (ws_bytes < L.bytes || cache_bytes < c.bytes) return MFGP_ERR_WORKSPACE;
+static int gpr_posterior_build_impl(mfgp_handle_t h, const GprProblem& P, void* cache, size_t cache_bytes) {
+    const GprLayout L = gpr_layout(h->nb, P, gpr_sched_no_flow(h));
+    const GprCache c = gpr_cache_layout(h->nb, P.nlf, P.n, P.p, P.d, cache);
+    if (P.ws_bytes < L.bytes || cache_bytes < c.bytes) return MFGP_ERR_WORKSPACE;
     hipStream_t s = h->stream;
-    gpr_factor(h->nb, s, L, n, p, d, X, ldx, Y, ldy, theta, info, nlf);
-    copy_block(s, X, ldx, c.X, d + 1, n, d + 1);
-    copy_block(s, theta, c.G, c.theta, c.G, 1, c.G);
+    gpr_factor(h->nb, s, L, P);
+    copy_block(s, P.X, P.ldx, c.X, P.d + 1, P.n, P.d + 1);
+    copy_block(s, P.theta, c.G, c.theta, c.G, 1, c.G);
     copy_block(s, L.Xo, c.ldr, c.LZ, c.ldr, c.npad, (int)c.ldr);
     return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
 }
@@ -437,11 +435,9 @@ int mfgp_gpr_posterior_size(mfgp_handle_t h, int nlf, int n, int p, int d, size_
 int mfgp_gpr_posterior_build(mfgp_handle_t h, int nlf, int n, int p, int d, const double* X, int ldx, const double* Y,
                              int ldy, const double* theta, void* ws, size_t ws_bytes, void* cache, size_t cache_bytes,
                              int* info) {
-    CHECK_H(h);
-    CHECK_D(d);
-    if (!gpr_geometry_ok(nlf, n, p) || !X || !Y || !theta || !ws || !cache || !info || ldx < d + 1 || ldy < p)
-        return MFGP_ERR_ARG;
-    return gpr_posterior_build_impl(h, nlf, n, p, d, X, ldx, Y, ldy, theta, ws, ws_bytes, cache, cache_bytes, info);
+    const GprProblem P{n, p, d, nlf, X, ldx, Y, ldy, theta, ws, ws_bytes, info};
+    if (const int rc = gpr_check(h, P, 0, cache && ldx >= d + 1 && ldy >= p)) return rc;
+    return gpr_posterior_build_impl(h, P, cache, cache_bytes);
 }
 
 int mfgp_gpr_posterior_predict_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar,

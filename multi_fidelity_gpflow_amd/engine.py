@@ -142,7 +142,7 @@ class Engine:
     def flow(self) -> bool:
         return self.lib.mfgp_get_flow(self.h) in (1, 3)
 
-    FLOW_MIN_TILES = 8   # mfgp_capi.hip: below this many 32-tiles mode 1 runs the step launches
+    FLOW_MIN_TILES = 8   # mfgp_host.h: below this many 32-tiles mode 1 runs the step launches
 
     def flow_runs(self, n: int) -> bool:
         """Whether an n-point fp64 factorization takes the persistent flow under the current mode."""

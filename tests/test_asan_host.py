@@ -1,5 +1,6 @@
 """Host-side coverage of libmfgp.so without a GPU: every workspace-size query over a sweep of
-problem sizes and settings (the layout carves of mfgp_capi.hip / mfgp_svgp*.hip / mfgp_f32.hip),
+problem sizes and settings (the layout carves of mfgp_gpr_capi.hip / mfgp_f32_capi.hip / mfgp_capi.hip /
+mfgp_svgp*.hip),
 argument validation of the compute entry points, and the handle settings.  Run as part of the CPU
 suite, and under AddressSanitizer by tools/asan_host.sh (a -fsanitize=address host build loaded
 through MFGP_LIB_PATH): any out-of-bounds host access in these paths aborts the run."""
