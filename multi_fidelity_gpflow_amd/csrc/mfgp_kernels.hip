@@ -1237,12 +1237,8 @@ __global__ __launch_bounds__(NTHREADS) void k_grad(GradArgs a) {
         const int gi = i * NB + r, gj = j * NB + r;
         stage(e, (gi < a.n) ? a.X[(long)gi * a.ldxx + d] : 0.0, (gj < a.n) ? a.X[(long)gj * a.ldxx + d] : 0.0);
     }
+    static_assert((MFGP_MAX_LF + 1) * MAXD <= NTHREADS, "one 1 / l^2 entry per thread: pl above holds them all");
     if (threadIdx.x < nsrc * a.D) il2[threadIdx.x] = 1.0 / (pl * pl);
-    for (int e = threadIdx.x + NTHREADS; e < nsrc * a.D; e += NTHREADS) {
-        const int src = e / a.D, d = e % a.D;
-        const double l = a.nlf ? a.theta[src * (1 + a.D) + 1 + d] : (src == 0 ? th.lL(d) : th.lD(d));
-        il2[e] = 1.0 / (l * l);
-    }
     __syncthreads();
 
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
