@@ -424,8 +424,12 @@ size_t gram_smem_bytes(int nb) {
 // Goku SingleBinSVGP Kuf: 64 latents x 300 x 1164).  64 x 64 entries per 256-thread workgroup:
 // lane = column (coalesced 512-B row stores), wave w = rows w, w+4, .., w+60; the column's scaled
 // row lives in registers (D4 = dimensions padded to 4, a template parameter), the row side is
-// read from LDS as a wave-wide broadcast.  Same arithmetic as gram_entry, bit for bit (same
-// scaling x * rcp_nr(l), same dot4 accumulation order, same expressions).
+// read from LDS as a wave-wide broadcast.  The arithmetic of gram_entry (same scaling
+// x * rcp_nr(l), same dot4 accumulation order, same expressions) on coordinates taken relative to
+// X1's first row: the expansion |a|^2 + |b|^2 - 2 a.b loses eps |x|^2 / l^2 of r^2, which at
+// coordinates of 1000 put the SVGP ELBO 4e-10 and its gradient 4e-7 of a component's mass off
+// (SVGP per-component bound); relative to a row of the data it loses eps times the
+// data's spread squared, wherever the data lie.  k_kgrad centres its operands the same way.
 // Entries with gi < wr1, gj < wr2 outside n1 x n2 are written 0.0 (the padded Kuf / Kmn buffers
 // need no memset), or 1.0 on the diagonal with GramArgs::padded (called directly, not through
 // launch_gram: the SVGP K_uu, whose padded rows factor as identity; with GramArgs::R it also
@@ -453,6 +457,7 @@ __global__ __launch_bounds__(NTHREADS) void k_gram_dense(GramArgs a, int wr1, in
     __shared__ __attribute__((aligned(16))) double sD2[GD_T * D4];
     __shared__ double nL1[GD_T], nD1[GD_T], f1[GD_T];
     __shared__ double il[2 * MAXD];
+    __shared__ double cz[MAXD];
     const int b = blockIdx.z, t = threadIdx.x;
     const int ti = blockIdx.x / tc, tj = blockIdx.x % tc;
     const int r0 = ti * GD_T, c0 = tj * GD_T;
@@ -463,6 +468,9 @@ __global__ __launch_bounds__(NTHREADS) void k_gram_dense(GramArgs a, int wr1, in
     if (t < D) {
         il[t] = rcp_nr(tp[1 + t]);
         il[MAXD + t] = a.rbf_only ? 1.0 : rcp_nr(tp[2 + D + t]);
+        // both sides' coordinates are taken relative to X1's first row: r^2 = |a|^2 + |b|^2 - 2 a.b
+        // cancels at the size of the coordinates, which then is the data's spread wherever the data lie
+        cz[t] = a.n1 > 0 ? X1[t] : 0.0;
     }
     const double vL = tp[0];
     const double vD = a.rbf_only ? 0.0 : tp[1 + D];
@@ -472,10 +480,10 @@ __global__ __launch_bounds__(NTHREADS) void k_gram_dense(GramArgs a, int wr1, in
     for (int e = t; e < GD_T * D4; e += NTHREADS) {
         const int r = e / D4, d = e % D4;
         const bool in = d < D;
-        const double x1 = (in && r0 + r < a.n1) ? X1[(long)(r0 + r) * a.ldx1 + d] : 0.0;
+        const double x1 = (in && r0 + r < a.n1) ? X1[(long)(r0 + r) * a.ldx1 + d] - cz[d] : 0.0;
         sL1[e] = in ? x1 * il[d] : 0.0;
         if (!a.rbf_only) {
-            const double x2 = (in && c0 + r < a.n2) ? X2[(long)(c0 + r) * a.ldx2 + d] : 0.0;
+            const double x2 = (in && c0 + r < a.n2) ? X2[(long)(c0 + r) * a.ldx2 + d] - cz[d] : 0.0;
             sD1[e] = in ? x1 * il[MAXD + d] : 0.0;
             sD2[e] = in ? x2 * il[MAXD + d] : 0.0;
         }
@@ -486,7 +494,7 @@ __global__ __launch_bounds__(NTHREADS) void k_gram_dense(GramArgs a, int wr1, in
     double bl[D4];
 #pragma unroll
     for (int d = 0; d < D4; ++d)
-        bl[d] = (d < D && gj < a.n2) ? X2[(long)gj * a.ldx2 + d] * il[d] : 0.0;
+        bl[d] = (d < D && gj < a.n2) ? (X2[(long)gj * a.ldx2 + d] - cz[d]) * il[d] : 0.0;
     const double f2 = (gj < a.n2) ? (a.rbf_only ? 0.0 : X2[(long)gj * a.ldx2 + D]) : -1.0;
     __syncthreads();
     if (t < GD_T) {
