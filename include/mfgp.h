@@ -257,6 +257,42 @@ int mfgp_mvn_sample(mfgp_handle_t h, int n, int batch, int nsamp, int ncol, cons
                     double jitter, const double* mean, long mean_rs, long mean_bs, const double* eps, double* out,
                     long rs, long ss, long bs, void* ws, size_t ws_bytes, int* info /* [batch] */);
 
+/* Batched Gaussian log-density with its gradients w.r.t. the mean and the variances: per row s < ns, with
+ *   Sigma_s = obs_cov + diag(f_var(s, .) + obs_var(s, .))  and  r = Y(s, .) - mean(s, .),
+ *   logp[s]     = -1/2 r^T Sigma_s^{-1} r - 1/2 log det Sigma_s - (p / 2) log 2 pi,
+ *   gmean[s][c] = a_c = (Sigma_s^{-1} r)_c                 (d logp / d mean = -d logp / d Y),
+ *   gvar[s][c]  = 1/2 (a_c^2 - (Sigma_s^{-1})_cc)          (d logp / d f_var(s, c)).
+ *   mean     [ns][ldm], ldm >= p.
+ *   Y        row s at s * y_rs; y_rs = 0: one shared vector (otherwise y_rs >= p).
+ *   var      f_var(s, c) at s * var_rs + c * var_cs, var_cs 0 or 1; var_cs = 0: one variance per row (GPR).
+ *   obs_var  [p] diagonal variances, row s at s * ov_rs (0: shared, otherwise >= p), or NULL.
+ *   obs_cov  [p][ldc] SPD, ldc >= p, only the lower triangle is read, or NULL.
+ *   gmean    [ns][ldgm] or NULL; gvar [ns][ldgv] or NULL (ldgm, ldgv >= p).  With var_cs = 0, ldgv = 1 is
+ *            accepted too: gvar[s] is then the derivative w.r.t. the row's one variance, the fixed-order sum
+ *            of the p columns (what mfgp_gpr_posterior_predict_vjp takes as gvar).
+ *   info     [ns]: 0, or the 1-based index of the first output with a non-positive / non-finite pivot (dense
+ *            form) or total variance (diagonal form) or a non-finite residual; that row's outputs are then
+ *            unspecified, the other rows are unaffected.
+ * Dense form (obs_cov given): p <= 128, beyond that MFGP_ERR_ARG -- the form is not built for larger p.  One
+ * workgroup per row: Sigma_s is formed in LDS, factored there in 8-column blocks with r carried along as one
+ * more row (the forward solve and the quadratic form come out of the factorization itself), and, with a
+ * gradient asked for, the factor is inverted in place.  The LDS size is chosen at launch from p (34 KB at
+ * p = 64: four workgroups per CU; 134 KB at p = 128).  Diagonal form (obs_cov NULL): any p, one wave per row,
+ * no factorization; an output whose target Y(s, c) is NaN is left out (no term, both gradients 0: a row with
+ * no target at all has logp = 0).  One launch either way.  Fixed-order sums and no floating-point atomics:
+ * a row's bits do not depend on ns or on the other rows.  Nothing is allocated, no synchronisation, no host
+ * read of a device word; the workspace is reserved (mfgp_mvn_logpdf_workspace_size; the kernels keep
+ * everything on chip).  ns = 0: a no-op (MFGP_OK, decided before the pointers are looked at).  A negative
+ * count, p < 1, a short leading dimension or stride, or a null required pointer: MFGP_ERR_ARG; a workspace
+ * smaller than the size call reports: MFGP_ERR_WORKSPACE; both before any device work.
+ * Replaces: gpflow GPModel.predict_log_density / Gaussian._predict_log_density (the diagonal form) and the
+ * torch.linalg.cholesky + cholesky_solve + autograd formulation of an emulator likelihood (the dense form). */
+int mfgp_mvn_logpdf_workspace_size(mfgp_handle_t h, int ns, int p, size_t* bytes);
+int mfgp_mvn_logpdf(mfgp_handle_t h, int ns, int p, const double* mean, int ldm, const double* Y, long y_rs,
+                    const double* var, long var_rs, long var_cs, const double* obs_var, long ov_rs,
+                    const double* obs_cov, int ldc, void* ws, size_t ws_bytes, double* logp, double* gmean, int ldgm,
+                    double* gvar, int ldgv, int* info /* [ns] */);
+
 /* SVGP ELBO value (GPflow SVGP.elbo, whiten=True, Gaussian likelihood) for the
  * latent LinearCoregionalization model (mfgpflow/linear_svgp.py:64-203) and the
  * SingleBinSVGP (SeparateIndependent, mfgpflow/singlebin_svgp.py:13-97, W = I):
@@ -456,6 +492,29 @@ int mfgp_svgp_posterior_predict_vjp(mfgp_handle_t h, int nstar, int m, int l, in
                                     const void* cache, size_t cache_bytes, const double* Xs, int ldxs, void* ws,
                                     size_t ws_bytes, double* f_mu, double* f_var, const double* gmean, int ldgm,
                                     const double* gvar, double* gX, int ldgx);
+
+/* Emulator log-likelihood from the cached posterior: logp[s] = log N(Y(s, .) | mean(Xs_s), diag(var(Xs_s) +
+ * obs_var(s, .)) + obs_cov), and optionally its gradient w.r.t. Xs, from one call.  Arguments as the predict
+ * calls, then Y / obs_var / obs_cov / logp / info as mfgp_mvn_logpdf takes them.  Enqueues, in order: the
+ * predict calls' own forward (mean / var, f_mu / f_var carry the predict calls' bits), the density launch
+ * on them, and -- with gX [nstar x (d + 1)] (ldgx) given -- k_post_grad fed the density's gmean / gvar,
+ * which live in the workspace (GPR: gvar is the [nstar] sum over the outputs that share the one variance).
+ * gX is bitwise what *_predict_vjp returns for those upstream gradients; the forward runs once.  gX = NULL:
+ * the call ends behind the density launch.  The emulator's own likelihood noise is NOT added: pass it in
+ * obs_var.  The graph kernel (nlf > 0) has the value only: a gX there is MFGP_ERR_ARG.  nstar = 0 is a
+ * no-op; argument and workspace errors as the VJP calls and mfgp_mvn_logpdf, before any device work. */
+int mfgp_gpr_posterior_logdens_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar,
+                                              size_t* bytes);
+int mfgp_gpr_posterior_logdens(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar, const void* cache,
+                               size_t cache_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes, double* mean,
+                               int ldm, double* var, const double* Y, long y_rs, const double* obs_var, long ov_rs,
+                               const double* obs_cov, int ldc, double* logp, double* gX, int ldgx, int* info);
+int mfgp_svgp_posterior_logdens_workspace_size(mfgp_handle_t h, int nstar, int m, int l, int p, int d, size_t* bytes);
+int mfgp_svgp_posterior_logdens(mfgp_handle_t h, int nstar, int m, int l, int p, int d, int mixed, const void* cache,
+                                size_t cache_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes,
+                                double* f_mu, double* f_var, const double* Y, long y_rs, const double* obs_var,
+                                long ov_rs, const double* obs_cov, int ldc, double* logp, double* gX, int ldgx,
+                                int* info);
 
 /* Leave-group-out cross-validation from a GPR cache, at the cache's hyper-parameters: for each group
  * S of training rows, what a model built without those rows predicts for them, in closed form from

@@ -60,6 +60,8 @@ SIGNATURES = {
     "mfgp_potrf_inv": [_p, _i, _i, _p, _i, _l, _p, _sz, _p, _i, _l, _p, _p],
     "mfgp_mvn_sample_workspace_size": [_p, _i, _i, C.POINTER(_sz)],
     "mfgp_mvn_sample": [_p, _i, _i, _i, _i, _p, _i, _l, _d, _p, _l, _l, _p, _p, _l, _l, _l, _p, _sz, _p],
+    "mfgp_mvn_logpdf_workspace_size": [_p, _i, _i, C.POINTER(_sz)],
+    "mfgp_mvn_logpdf": [_p, _i, _i, _p, _i, _p, _l, _p, _l, _l, _p, _l, _p, _i, _p, _sz, _p, _p, _i, _p, _i, _p],
     "mfgp_svgp_workspace_size": [_p, _i, _i, _i, _i, _i, C.POINTER(_sz)],
     "mfgp_svgp_elbo": [_p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _d, _d, _d, _p, _sz, _p,
                        _p, _p, _p],
@@ -102,6 +104,12 @@ SIGNATURES = {
     "mfgp_svgp_posterior_predict_vjp_workspace_size": [_p, _i, _i, _i, _i, _i, C.POINTER(_sz)],
     "mfgp_svgp_posterior_predict_vjp": [_p, _i, _i, _i, _i, _i, _i, _p, _sz, _p, _i, _p, _sz, _p, _p, _p, _i, _p, _p,
                                         _i],
+    "mfgp_gpr_posterior_logdens_workspace_size": [_p, _i, _i, _i, _i, _i, C.POINTER(_sz)],
+    "mfgp_gpr_posterior_logdens": [_p, _i, _i, _i, _i, _i, _p, _sz, _p, _i, _p, _sz, _p, _i, _p, _p, _l, _p, _l, _p,
+                                   _i, _p, _p, _i, _p],
+    "mfgp_svgp_posterior_logdens_workspace_size": [_p, _i, _i, _i, _i, _i, C.POINTER(_sz)],
+    "mfgp_svgp_posterior_logdens": [_p, _i, _i, _i, _i, _i, _i, _p, _sz, _p, _i, _p, _sz, _p, _p, _p, _l, _p, _l, _p,
+                                    _i, _p, _p, _i, _p],
     "mfgp_gpr_posterior_leave_out_workspace_size": [_p, _i, _i, _i, _i, _i, _i, C.POINTER(_sz)],
     "mfgp_gpr_posterior_leave_out": [_p, _i, _i, _i, _i, _p, _sz, _i, _p, _p, _i, _i, _p, _sz, _p, _i, _p, _i, _p,
                                      _p],

@@ -5,6 +5,7 @@
 //   mfgp_gpr_capi.hip        fp64 GPR / graph-kernel training and predict: gpr_layout, gpr_factor
 //   mfgp_f32_capi.hip        the fp32 path, the fp32 settings and the dtype-generic *_ex entries
 //   mfgp_posterior_capi.hip  the cached posterior
+//   mfgp_density.hip         mfgp_mvn_logpdf, beside its kernels
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -573,4 +573,24 @@ struct SampleArgs {
 size_t mvn_sample_ws_bytes(int n, int batch);
 void launch_mvn_sample(SampleArgs a, void* ws, hipStream_t s);
 
+// mfgp_mvn_logpdf (mfgp_density.hip): the Gaussian log-density of row s of Y under N(mean_s, obs_cov +
+// diag(var_s + obs_var_s)) and its gradients w.r.t. mean and var; the addressing is include/mfgp.h's.
+constexpr int MVN_DENSE_MAXP = 128;            // the dense form's LDS image: 129 x 129 doubles
+constexpr size_t MVN_LOGPDF_WS_BYTES = 256;    // reserved: the kernels keep everything on chip
+struct LogpdfArgs {
+    int ns, p;
+    const double* mean; long ldm;
+    const double* Y; long y_rs;
+    const double* var; long var_rs, var_cs;
+    const double* obs_var; long ov_rs;        // nullptr: none
+    const double* obs_cov; long ldc;          // nullptr: the diagonal form
+    double* logp;
+    double* gmean; long ldgm;                 // nullptr: not wanted
+    double* gvar; long ldgv;                  // nullptr: not wanted
+    int gv_sum;                               // 1 (var_cs == 0 only): gvar is [ns], summed over the outputs
+    int* info;
+};
+void launch_mvn_logpdf(const LogpdfArgs& a, hipStream_t s);
+bool mvn_logpdf_geometry_ok(int ns, int p, bool dense, int ldc, long y_rs, long ov_rs);
+
 }  // namespace mfgp

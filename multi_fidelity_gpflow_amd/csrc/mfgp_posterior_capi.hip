@@ -1,5 +1,5 @@
 // C-ABI entry points of the cached posterior (include/mfgp.h, mfgp_gpr_posterior_size through
-// mfgp_svgp_posterior_predict_vjp): the cache and workspace layouts, the argument blocks and the launch
+// mfgp_svgp_posterior_logdens): the cache and workspace layouts, the argument blocks and the launch
 // sequences of mfgp_posterior.hip / mfgp_leave_out.hip / mfgp_design.hip / mfgp_append.hip.  Host-side
 // orchestration only, as the other *_capi.hip files: no allocation, no synchronisation.
 #include <algorithm>
@@ -162,6 +162,71 @@ static int gpr_posterior_predict_impl(mfgp_handle_t h, int nlf, int n, int p, in
     launch_post<NB>(a, 1, s);
     if (g) launch_post_grad<NB>(a, 1, s);
     if (cov) cov_from_a<NB>(s, Xs, ldxs, nstar, c.theta, d, nlf, P.Am, P.nspad, c.T, P.Kss, P.Cov, cov, ldc);
+    return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
+}
+
+// The log-density calls: the forward, the density launch on its mean / var (mfgp_density.hip), then --
+// with an input gradient asked for -- k_post_grad fed the density's own gradients.  Their workspace is the
+// predict (value only) or predict-VJP layout, then gmean [nstar x p] and gvar (GPR: [nstar], the sum over
+// the outputs that share the one variance; SVGP: [nstar x p]).
+struct LogdensIO {
+    const double* Y; long y_rs;
+    const double* obs_var; long ov_rs;
+    const double* obs_cov; int ldc;
+    double* logp;
+    double* gX; int ldgx;     // nullptr: the value only, the call ends behind the density launch
+    int* info;
+};
+struct LogdensLayout {
+    double *gm, *gv;
+    size_t bytes;
+};
+static LogdensLayout logdens_layout(size_t base, int nstar, int p, bool svgp, void* ws) {
+    LogdensLayout L{};
+    const size_t o = (base + 255) & ~(size_t)255;
+    Carve c(ws ? (char*)ws + o : nullptr);
+    L.gm = c.take<double>((size_t)nstar * p);
+    L.gv = c.take<double>((size_t)nstar * (svgp ? p : 1));
+    L.bytes = o + c.off + 256;
+    return L;
+}
+static bool logdens_io_ok(const LogdensIO& q, int nstar, int p, int d) {
+    return mvn_logpdf_geometry_ok(nstar, p, q.obs_cov != nullptr, q.ldc, q.y_rs, q.ov_rs) && q.Y && q.logp && q.info &&
+           (!q.gX || q.ldgx >= d + 1);
+}
+// the density launch on the forward's outputs; grad: its gradients into the workspace block L
+static void logdens_launch(hipStream_t s, const LogdensIO& q, const LogdensLayout& L, int nstar, int p,
+                           const double* mean, long ldm, const double* var, bool svgp) {
+    LogpdfArgs a{};
+    a.ns = nstar; a.p = p;
+    a.mean = mean; a.ldm = ldm;
+    a.Y = q.Y; a.y_rs = q.y_rs;
+    a.var = var; a.var_rs = svgp ? p : 1; a.var_cs = svgp ? 1 : 0;
+    a.obs_var = q.obs_var; a.ov_rs = q.ov_rs;
+    a.obs_cov = q.obs_cov; a.ldc = q.ldc;
+    a.logp = q.logp; a.info = q.info;
+    if (q.gX) {
+        a.gmean = L.gm; a.ldgm = p;
+        a.gvar = L.gv; a.ldgv = svgp ? p : 1; a.gv_sum = svgp ? 0 : 1;
+    }
+    launch_mvn_logpdf(a, s);
+}
+
+template <int NB>
+static int gpr_posterior_logdens_impl(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar, const void* cache,
+                                      size_t cache_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes,
+                                      double* mean, int ldm, double* var, const LogdensIO& q) {
+    const GprCache c = gpr_cache_layout(NB, nlf, n, p, d, cache);
+    const PostLayout P = post_layout(NB, c.T, c.Tp, nstar, 1, false, ws);
+    const PostGradLayout G = post_grad_layout(NB, P, c.T, d, 1, false, ws);
+    const LogdensLayout L = logdens_layout(G.bytes, nstar, p, false, ws);
+    if (cache_bytes < c.bytes || ws_bytes < (q.gX ? L.bytes : P.bytes)) return MFGP_ERR_WORKSPACE;
+    hipStream_t s = h->stream;
+    PostArgs a = gpr_post_args(c, P, Xs, ldxs, nstar, mean, ldm, var, q.gX != nullptr);
+    if (q.gX) post_grad_args(a, G, PostGradIO{L.gm, p, L.gv, q.gX, q.ldgx});
+    launch_post<NB>(a, 1, s);
+    logdens_launch(s, q, L, nstar, p, mean, ldm, var, false);
+    if (q.gX) launch_post_grad<NB>(a, 1, s);
     return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
 }
 
@@ -379,11 +444,15 @@ static int svgp_posterior_build_impl(mfgp_handle_t h, int m, int l, int p, int d
 static int svgp_posterior_predict_impl(mfgp_handle_t h, int nstar, int m, int l, int p, int d, int mixed,
                                        const void* cache, size_t cache_bytes, const double* Xs, int ldxs, void* ws,
                                        size_t ws_bytes, double* f_mu, double* f_var,
-                                       const PostGradIO* g = nullptr) {
+                                       const PostGradIO* g = nullptr, const LogdensIO* q = nullptr) {
     const SvgpCache c = svgp_cache_layout(h->nb, m, l, p, d, cache);
     const PostLayout P = post_layout(h->nb, c.Tm, 0, nstar, l, true, ws);
     const PostGradLayout G = post_grad_layout(h->nb, P, c.Tm, d, l, true, ws);
-    if (cache_bytes < c.bytes || ws_bytes < (g ? G.bytes : P.bytes)) return MFGP_ERR_WORKSPACE;
+    const LogdensLayout Q = logdens_layout(G.bytes, nstar, p, true, ws);
+    // the log-density call with an input gradient is the VJP call fed the density's own gradients
+    const PostGradIO qg{Q.gm, p, Q.gv, q ? q->gX : nullptr, q ? q->ldgx : 0};
+    if (q && q->gX) g = &qg;
+    if (cache_bytes < c.bytes || ws_bytes < (q && q->gX ? Q.bytes : g ? G.bytes : P.bytes)) return MFGP_ERR_WORKSPACE;
     const long mm = (long)c.mpad * c.mpad;
     PostArgs a{};
     a.Li = c.Li; a.ldl = c.mpad; a.sL = mm;
@@ -403,6 +472,7 @@ static int svgp_posterior_predict_impl(mfgp_handle_t h, int nstar, int m, int l,
         post_grad_args(a, G, *g);
     }
     TILE_CALL(h->nb, launch_post, a, l, h->stream);
+    if (q) logdens_launch(h->stream, *q, Q, nstar, p, f_mu, p, f_var, true);
     if (g) TILE_CALL(h->nb, launch_post_grad, a, l, h->stream);
     return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
 }
@@ -656,6 +726,63 @@ int mfgp_svgp_posterior_predict_vjp(mfgp_handle_t h, int nstar, int m, int l, in
     const PostGradIO g{gmean, ldgm, gvar, gX, ldgx};
     return svgp_posterior_predict_impl(h, nstar, m, l, p, d, mixed, cache, cache_bytes, Xs, ldxs, ws, ws_bytes, f_mu,
                                        f_var, &g);
+}
+
+int mfgp_gpr_posterior_logdens_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar,
+                                              size_t* bytes) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (!gpr_geometry_ok(nlf, n, p) || nstar < 1 || !bytes) return MFGP_ERR_ARG;
+    const GprCache c = gpr_cache_layout(h->nb, nlf, n, p, d, nullptr);
+    const PostLayout P = post_layout(h->nb, c.T, c.Tp, nstar, 1, false, nullptr);
+    // (the graph kernel has the value only: the predict layout)
+    *bytes = nlf ? P.bytes
+                 : logdens_layout(post_grad_layout(h->nb, P, c.T, d, 1, false, nullptr).bytes, nstar, p, false, nullptr)
+                       .bytes;
+    return MFGP_OK;
+}
+
+int mfgp_gpr_posterior_logdens(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar, const void* cache,
+                               size_t cache_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes, double* mean,
+                               int ldm, double* var, const double* Y, long y_rs, const double* obs_var, long ov_rs,
+                               const double* obs_cov, int ldc, double* logp, double* gX, int ldgx, int* info) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (!nlf_ok(nlf) || (nlf != 0 && gX)) return MFGP_ERR_ARG;   // the graph kernel has no input gradient
+    if (nstar == 0) return MFGP_OK;
+    const LogdensIO q{Y, y_rs, obs_var, ov_rs, obs_cov, ldc, logp, gX, ldgx, info};
+    if (!gpr_geometry_ok(nlf, n, p) || nstar < 0 || !cache || !Xs || !ws || !mean || !var || ldxs < d + 1 || ldm < p ||
+        !logdens_io_ok(q, nstar, p, d))
+        return MFGP_ERR_ARG;
+    return TILE_CALL(h->nb, gpr_posterior_logdens_impl, h, nlf, n, p, d, nstar, cache, cache_bytes, Xs, ldxs, ws,
+                     ws_bytes, mean, ldm, var, q);
+}
+
+int mfgp_svgp_posterior_logdens_workspace_size(mfgp_handle_t h, int nstar, int m, int l, int p, int d, size_t* bytes) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nstar < 1 || m < 1 || l < 1 || p < 1 || !bytes) return MFGP_ERR_ARG;
+    const int T = ceil_div(m, h->nb);
+    const PostLayout P = post_layout(h->nb, T, 0, nstar, l, true, nullptr);
+    *bytes = logdens_layout(post_grad_layout(h->nb, P, T, d, l, true, nullptr).bytes, nstar, p, true, nullptr).bytes;
+    return MFGP_OK;
+}
+
+int mfgp_svgp_posterior_logdens(mfgp_handle_t h, int nstar, int m, int l, int p, int d, int mixed, const void* cache,
+                                size_t cache_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes,
+                                double* f_mu, double* f_var, const double* Y, long y_rs, const double* obs_var,
+                                long ov_rs, const double* obs_cov, int ldc, double* logp, double* gX, int ldgx,
+                                int* info) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nstar == 0) return MFGP_OK;
+    const LogdensIO q{Y, y_rs, obs_var, ov_rs, obs_cov, ldc, logp, gX, ldgx, info};
+    if (nstar < 0 || m < 1 || l < 1 || p < 1 || !cache || !Xs || !ws || !f_mu || !f_var || ldxs < d + 1 ||
+        !logdens_io_ok(q, nstar, p, d))
+        return MFGP_ERR_ARG;
+    if (!mixed && l != p) return MFGP_ERR_ARG;
+    return svgp_posterior_predict_impl(h, nstar, m, l, p, d, mixed, cache, cache_bytes, Xs, ldxs, ws, ws_bytes, f_mu,
+                                       f_var, nullptr, &q);
 }
 
 }  // extern "C"

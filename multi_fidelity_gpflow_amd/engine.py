@@ -422,6 +422,61 @@ class Engine:
                                        ptr(info)), "mfgp_mvn_sample")
         return out, info
 
+    def _density_args(self, what, ns, p, Y, obs_var, obs_cov):
+        """The Y / obs_var / obs_cov arguments of mfgp_mvn_logpdf and the fused posterior entries as
+        (tensors kept alive, (Y, y_rs, obs_var, ov_rs, obs_cov, ldc)): fp64 device tensors, Y [p] or [ns, p],
+        obs_var None / [p] / [ns, p], obs_cov None / [p, p] (unit inner stride; a row stride >= p is passed
+        on as ldc, so a block of a wider matrix is read in place)."""
+        def rows(t, name):
+            if t.dim() == 1 and t.shape[0] == p:
+                return t.contiguous(), 0
+            if t.dim() == 2 and tuple(t.shape) == (ns, p):
+                return t.contiguous(), p
+            raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected ({p},) or ({ns}, {p})")
+        Y, y_rs = rows(Y, "Y")
+        ov, ov_rs = (None, 0) if obs_var is None else rows(obs_var, "obs_var")
+        ldc = 0
+        if obs_cov is not None:
+            if tuple(obs_cov.shape) != (p, p):
+                raise ValueError(f"{what}: obs_cov has shape {tuple(obs_cov.shape)}, expected ({p}, {p})")
+            if p > 128:
+                raise ValueError(f"{what}: the dense form (obs_cov) is built for P <= 128 outputs, got {p}")
+            if (p > 1 and obs_cov.stride(1) != 1) or obs_cov.stride(0) < p:
+                obs_cov = obs_cov.contiguous()
+            ldc = max(obs_cov.stride(0), p)
+        return (Y, ov, obs_cov), (ptr(Y), y_rs, ptr(ov), ov_rs, ptr(obs_cov), ldc)
+
+    def mvn_logpdf(self, mean, Y, var, obs_var=None, obs_cov=None, grad=False, sum_gvar=False):
+        """Batched Gaussian log-density (include/mfgp.h mfgp_mvn_logpdf): mean [ns, p], Y [p] (shared) or
+        [ns, p], var [ns] (one variance per row, GPR) or [ns, p], obs_var / obs_cov as _density_args ->
+        (logp [ns], gmean, gvar, info [ns] int32).  grad: gmean [ns, p] = d logp / d mean and gvar [ns, p]
+        = d logp / d var per output; sum_gvar (var [ns] only): gvar [ns], the kernel's own fixed-order sum
+        over the outputs (what the GPR VJP takes).  Without grad both are None.  obs_cov None: the diagonal
+        form, NaN targets left out.  No host read of a device word."""
+        if mean.dim() != 2:
+            raise ValueError(f"mvn_logpdf: mean has shape {tuple(mean.shape)}, expected [ns, p]")
+        ns, p = mean.shape
+        if var.dim() == 1 and var.shape[0] == ns:
+            var_rs, var_cs = 1, 0
+        elif tuple(var.shape) == (ns, p):
+            var_rs, var_cs = p, 1
+        else:
+            raise ValueError(f"mvn_logpdf: var has shape {tuple(var.shape)}, expected ({ns},) or ({ns}, {p})")
+        if sum_gvar and var_cs != 0:
+            raise ValueError("mvn_logpdf: sum_gvar needs var [ns] (one variance per row)")
+        keep, dargs = self._density_args("mvn_logpdf", ns, p, Y, obs_var, obs_cov)
+        mean, var = mean.contiguous(), var.contiguous()
+        f64 = dict(dtype=torch.float64, device=self.device)
+        logp = torch.empty((ns,), **f64)
+        info = torch.zeros((ns,), dtype=torch.int32, device=self.device)
+        gmean = torch.empty((ns, p), **f64) if grad else None
+        gvar = torch.empty((ns,) if sum_gvar else (ns, p), **f64) if grad else None
+        ws = self.workspace("mvn_logpdf", self._size(self.lib.mfgp_mvn_logpdf_workspace_size, ns, p))
+        check(self.lib.mfgp_mvn_logpdf(self.h, ns, p, ptr(mean), p, dargs[0], dargs[1], ptr(var), var_rs, var_cs,
+                                       *dargs[2:], ptr(ws), ws.numel(), ptr(logp), ptr(gmean), p, ptr(gvar),
+                                       1 if sum_gvar else p, ptr(info)), "mfgp_mvn_logpdf")
+        return logp, gmean, gvar, info
+
     @staticmethod
     def _check_yunc(Yunc, Y, n, p):
         """The heteroscedastic entry points' Yunc: fp64 [n, >= p] on Y's device, unit inner stride."""
@@ -714,6 +769,45 @@ class Engine:
         check(getattr(self.lib, name)(self.h, ns, m, L, p, d, 1 if mixed else 0, ptr(cache), cache.numel(), ptr(Xs),
                                       Xs.shape[1], ptr(ws), ws.numel(), ptr(f_mu), ptr(f_var), *tail), name)
         return f_mu, f_var, gX
+
+    def gpr_posterior_logdens(self, nlf, shape, cache, Xs, Y, obs_var=None, obs_cov=None, grad=False):
+        """mfgp_gpr_posterior_logdens: the forward, the density launch and (grad) k_post_grad in one call ->
+        (mean [ns, p], var [ns], logp [ns], grad_X [ns, d + 1] or None, info [ns] int32).  Y / obs_var /
+        obs_cov as _density_args.  No host read of a device word."""
+        n, p, d = shape
+        ns = Xs.shape[0]
+        f64 = dict(dtype=torch.float64, device=self.device)
+        mean, var, logp = torch.empty((ns, p), **f64), torch.empty((ns,), **f64), torch.empty((ns,), **f64)
+        gX = torch.empty((ns, d + 1), **f64) if grad else None
+        info = torch.zeros((ns,), dtype=torch.int32, device=self.device)
+        keep, dargs = self._density_args("log_density", ns, p, Y, obs_var, obs_cov)
+        if ns == 0:
+            return mean, var, logp, gX, info
+        ws = self.workspace("post_logdens", self._size(self.lib.mfgp_gpr_posterior_logdens_workspace_size, nlf, n, p,
+                                                       d, ns))
+        check(self.lib.mfgp_gpr_posterior_logdens(self.h, nlf, n, p, d, ns, ptr(cache), cache.numel(), ptr(Xs),
+                                                  Xs.shape[1], ptr(ws), ws.numel(), ptr(mean), p, ptr(var), *dargs,
+                                                  ptr(logp), ptr(gX), d + 1, ptr(info)), "mfgp_gpr_posterior_logdens")
+        return mean, var, logp, gX, info
+
+    def svgp_posterior_logdens(self, shape, cache, Xs, Y, obs_var=None, obs_cov=None, grad=False):
+        """mfgp_svgp_posterior_logdens -> (f_mu [ns, p], f_var [ns, p], logp [ns], grad_X or None, info [ns])."""
+        m, L, p, d, mixed = shape
+        ns = Xs.shape[0]
+        f64 = dict(dtype=torch.float64, device=self.device)
+        f_mu, f_var, logp = torch.empty((ns, p), **f64), torch.empty((ns, p), **f64), torch.empty((ns,), **f64)
+        gX = torch.empty((ns, d + 1), **f64) if grad else None
+        info = torch.zeros((ns,), dtype=torch.int32, device=self.device)
+        keep, dargs = self._density_args("log_density", ns, p, Y, obs_var, obs_cov)
+        if ns == 0:
+            return f_mu, f_var, logp, gX, info
+        ws = self.workspace("post_logdens", self._size(self.lib.mfgp_svgp_posterior_logdens_workspace_size, ns, m, L,
+                                                       p, d))
+        check(self.lib.mfgp_svgp_posterior_logdens(self.h, ns, m, L, p, d, 1 if mixed else 0, ptr(cache),
+                                                   cache.numel(), ptr(Xs), Xs.shape[1], ptr(ws), ws.numel(), ptr(f_mu),
+                                                   ptr(f_var), *dargs, ptr(logp), ptr(gX), d + 1, ptr(info)),
+              "mfgp_svgp_posterior_logdens")
+        return f_mu, f_var, logp, gX, info
 
     def selftest_mfma(self) -> np.ndarray:
         out = torch.zeros((16, 16), dtype=torch.float64, device=self.device)

@@ -20,7 +20,8 @@ from .engine import Engine, to_dev
 from .kernels import GraphMultiFidelityKernel
 from ._lib import info_error
 from .models import Gaussian
-from .posteriors import DEFAULT_SAMPLE_JITTER, GPRPosterior, PrecomputeCacheType, draw_f_samples
+from .posteriors import (DEFAULT_SAMPLE_JITTER, GPRPosterior, PrecomputeCacheType, draw_f_samples,
+                         predict_log_density_of)
 from .params import (Module, Sigmoid, Softplus, as_result, gather_entries, scatter_entries, set_trainable,
                      tie_entries)
 from .session import _PackedAdam, _Session, check_outcome, span_from_tie
@@ -118,6 +119,12 @@ class GraphMultiFidelityGPModel(Module):
                                       "full_cov=False and full_output_cov=False")
         mean, var = self.predict_f(Xnew)
         return mean, as_result(var + float(self.likelihood.variance.numpy()))
+
+    def predict_log_density(self, data, full_cov: bool = False, full_output_cov: bool = False):
+        """GPflow GPModel.predict_log_density((Xnew, Ynew)): [N*], the log-density of Ynew under predict_y's
+        marginals summed over the outputs (mfgp_mvn_logpdf, the diagonal form).  Either covariance flag
+        raises NotImplementedError."""
+        return predict_log_density_of(self, self.predict_f, data, full_cov, full_output_cov)
 
     def predict_f_samples(self, Xnew, num_samples=None, full_cov: bool = True, full_output_cov: bool = False, *,
                           eps=None, generator=None, jitter: float = DEFAULT_SAMPLE_JITTER):

@@ -31,7 +31,8 @@ from .engine import AdamState, Engine, resolve_dtype, theta_size, to_dev
 from .kernels import LinearMultiFidelityKernel
 from .params import (Module, Parameter, as_result, gather_entries, positive, scatter_entries, set_trainable,
                      tie_entries)
-from .posteriors import DEFAULT_SAMPLE_JITTER, GPRPosterior, PrecomputeCacheType, draw_f_samples
+from .posteriors import (DEFAULT_SAMPLE_JITTER, GPRPosterior, PrecomputeCacheType, draw_f_samples,
+                         predict_log_density_of)
 from .session import (CholeskyError, _Session, _StepRunner, _retire_graphs, _retired_graphs,  # noqa: F401
                       check_outcome, new_stream, release_retired_graphs)
 
@@ -228,6 +229,12 @@ class MultiFidelityGPModel(Module):
                                       "full_cov=False and full_output_cov=False")
         mean, var = self.predict_f(Xnew)
         return mean, as_result(var + float(self.likelihood.variance.numpy()))
+
+    def predict_log_density(self, data, full_cov: bool = False, full_output_cov: bool = False):
+        """GPflow GPModel.predict_log_density((Xnew, Ynew)): [N*], the log-density of Ynew under predict_y's
+        marginals summed over the outputs (mfgp_mvn_logpdf, the diagonal form; a float32 model casts its
+        mean / var to float64 for this call).  Either covariance flag raises NotImplementedError."""
+        return predict_log_density_of(self, self.predict_f, data, full_cov, full_output_cov)
 
     def predict_f_samples(self, Xnew, num_samples=None, full_cov: bool = True, full_output_cov: bool = False, *,
                           eps=None, generator=None, jitter: float = DEFAULT_SAMPLE_JITTER):

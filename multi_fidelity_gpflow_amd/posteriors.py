@@ -30,6 +30,12 @@ Joint draws: ``predict_f_samples(Xnew, num_samples)`` is GPflow's ``sample_mvn``
 the matrix core).  A GPR posterior factors its one [N*, N*] block once for all P outputs; an SVGP posterior
 factors the snapshot's [P, N*, N*].  ``eps=`` passes the standard-normal input (a deterministic call);
 the four models have the same method at their current parameters.
+
+Inference: ``log_density(Xnew, Y, obs_cov, obs_var, grad)`` is the emulator log-likelihood of one data vector
+(or one per row) at every row of ``Xnew`` -- a batch of MCMC / HMC walkers -- and its exact input gradient, from
+one call (``mfgp_*_posterior_logdens``: the forward once, a batched [P, P] density kernel in LDS
+(``mfgp_mvn_logpdf``), then the VJP kernel fed the density's own gradients).  ``predict_log_density`` is GPflow's
+method of that name on the marginal prediction, for the four models and both posterior classes.
 """
 from __future__ import annotations
 
@@ -161,6 +167,126 @@ def draw_f_samples(p, inputs, marginal, joint, Xnew, num_samples, full_cov, full
         return sample_marginal(mean, var, e, num_samples is None)
     mean, cov, ncol, pre = joint(eng, Xs)
     return sample_joint(eng, what, mean, cov, e, ncol, jitter, num_samples is None, pre)
+
+
+MAX_DENSE_OUTPUTS = 128   # outputs of the dense log-density form (include/mfgp.h mfgp_mvn_logpdf: p <= 128)
+
+
+class LogDensityResult(NamedTuple):
+    """What ``log_density`` returns (device tensors, detached)."""
+    logp: torch.Tensor                      # [N*] log N(Y | mean, diag(var + obs_var) + obs_cov)
+    mean: torch.Tensor                      # [N*, P] predict_f's mean (the same bits)
+    var: torch.Tensor                       # [N*, P] predict_f's marginal variance (the same bits)
+    grad_X: Optional[torch.Tensor] = None   # [N*, D + 1] d logp / d Xnew (fidelity column 0), with grad=True
+
+
+def _shape_of(x):
+    return tuple(x.shape) if isinstance(x, torch.Tensor) else np.shape(x)
+
+
+def _on_host(x) -> bool:
+    return not (isinstance(x, torch.Tensor) and x.device.type != "cpu")
+
+
+def density_plan(what, ns, p, Y, obs_var, obs_cov):
+    """The argument checks of log_density's Y / obs_var / obs_cov, all on the host before any device work.
+    ValueError for a Y that is not [P] or [N*, P], an obs_var that is no scalar, [P] or
+    [N*, P] or holds a negative (or NaN) entry, an obs_cov that is not [P, P], or P > 128 with obs_cov.
+    (The sign of an obs_var that already lives on the device is not read back: a non-positive total
+    variance shows in the call's info.)"""
+    ys = _shape_of(Y)
+    if ys != (p,) and ys != (ns, p):
+        raise ValueError(f"{what}: Y has shape {ys}, expected ({p},) or ({ns}, {p})")
+    if obs_var is not None:
+        vs = _shape_of(obs_var)
+        if vs not in ((), (p,), (ns, p)):
+            raise ValueError(f"{what}: obs_var has shape {vs}, expected a scalar, ({p},) or ({ns}, {p})")
+        if _on_host(obs_var):
+            v = obs_var.detach().numpy() if isinstance(obs_var, torch.Tensor) else np.asarray(obs_var, dtype=np.float64)
+            if not np.all(v >= 0):
+                raise ValueError(f"{what}: obs_var must be non-negative (and not NaN)")
+    if obs_cov is not None:
+        cs = _shape_of(obs_cov)
+        if cs != (p, p):
+            raise ValueError(f"{what}: obs_cov has shape {cs}, expected ({p}, {p})")
+        if p > MAX_DENSE_OUTPUTS:
+            raise ValueError(f"{what}: the dense form (obs_cov) is built for P <= {MAX_DENSE_OUTPUTS} outputs, "
+                             f"got {p}; pass a diagonal obs_var instead")
+
+
+def density_inputs(eng: Engine, p, Y, obs_var, obs_cov):
+    """(Y, obs_var, obs_cov) as fp64 device tensors (a scalar obs_var becomes [P]; an fp64 device obs_cov is
+    passed as it is, strides and all)."""
+    Yd = to_dev(Y, eng.device)
+    ov = None
+    if obs_var is not None:
+        ov = to_dev(obs_var, eng.device)
+        if ov.dim() == 0:
+            ov = ov.expand(p).contiguous()
+    oc = None
+    if obs_cov is not None:
+        if isinstance(obs_cov, torch.Tensor) and obs_cov.device == eng.device and obs_cov.dtype == torch.float64:
+            oc = obs_cov.detach()
+        else:
+            oc = to_dev(obs_cov, eng.device)
+    return Yd, ov, oc
+
+
+def raise_density_info(what, info, dense):
+    """The one host read of a log-density call, after everything is enqueued."""
+    bad = info.cpu().numpy()
+    if np.any(bad != 0):
+        s = int(np.flatnonzero(bad)[0])
+        kind = ("the Cholesky decomposition of its covariance was not successful" if dense
+                else "its total variance is not positive")
+        raise CholeskyError(f"{what}: row {s}: {kind} (or its residual is not finite) at output {int(bad[s]) - 1}; "
+                            "the input might not be valid.")
+
+
+def predict_log_density_of(model, predict_f, data, full_cov=False, full_output_cov=False):
+    """GPflow ``GPModel.predict_log_density`` with the Gaussian likelihoods of this package: the marginal
+    ``predict_f`` at Xnew, then ``sum_c log N(Y[s, c] | mean[s, c], var[s, c] + s2[s, c])`` on the device
+    (mfgp_mvn_logpdf, the diagonal form), [N*].  s2 is the likelihood variance of ``model`` now:
+    ``Gaussian`` its scalar; ``HeteroscedasticGaussian`` the baseline for [N*, P] targets and baseline +
+    Y_unc**2 for [N*, 2P] targets [Y_obs | Y_unc]; ``MaskedGaussian`` each output's own, NaN targets left
+    out (any other likelihood: a NaN target gives a NaN row, as GPflow's does)."""
+    from .models import HeteroscedasticGaussian, MaskedGaussian
+    what = "predict_log_density"
+    if full_cov or full_output_cov:
+        raise NotImplementedError("The predict_log_density method currently supports only the argument values "
+                                  "full_cov=False and full_output_cov=False")
+    try:
+        Xnew, Ynew = data
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: data must be the pair (Xnew, Ynew)") from None
+    lik = model.likelihood
+    p = int(getattr(model, "num_outputs", None) or model.num_output_dims)
+    xs, ys = _shape_of(Xnew), _shape_of(Ynew)
+    if len(xs) != 2:
+        raise ValueError(f"{what}: Xnew has shape {xs}, expected [N*, D + 1]")
+    ns = int(xs[0])
+    het = isinstance(lik, HeteroscedasticGaussian)
+    masked = isinstance(lik, MaskedGaussian)
+    if ys != (ns, p) and not (het and ys == (ns, 2 * p)) and not (p == 1 and ys == (ns,)):
+        want = f"({ns}, {p})" + (f" or ({ns}, {2 * p})" if het else "")
+        raise ValueError(f"{what}: Ynew has shape {ys}, expected {want}")
+    s2 = np.ascontiguousarray(np.reshape(lik.variance.numpy(), -1), dtype=np.float64)
+    if s2.size not in (1, p):
+        raise ValueError(f"{what}: the likelihood variance has {s2.size} entries, expected 1 or {p}")
+    mean, var = predict_f(Xnew)   # every ValueError of the arguments is raised above
+    mean = mean.as_subclass(torch.Tensor).detach().to(torch.float64)   # (an fp32 model: cast for this call)
+    var = var.as_subclass(torch.Tensor).detach().to(torch.float64)
+    eng = Engine.get(mean.device)
+    Yd = to_dev(Ynew, eng.device).reshape(ns, -1)
+    ov = to_dev(np.broadcast_to(s2, (p,)).copy(), eng.device)
+    if het and Yd.shape[1] == 2 * p:
+        ov = ov[None, :] + Yd[:, p:] ** 2
+        Yd = Yd[:, :p]
+    logp, _, _, info = eng.mvn_logpdf(mean, Yd, var, obs_var=ov)
+    if not masked:
+        logp = torch.where(torch.isnan(Yd).any(dim=1), torch.full_like(logp, float("nan")), logp)
+    raise_density_info(what, info, False)
+    return as_result(logp)
 
 
 MAX_GROUP = 32   # rows of one left-out group (include/mfgp.h mfgp_gpr_posterior_leave_out: gmax <= 32)
@@ -417,6 +543,49 @@ class _Posterior:
         return draw_f_samples(self._num_outputs(), inputs, self.predict_f, self._joint, Xnew, num_samples, full_cov,
                               full_output_cov, eps, generator, jitter)
 
+    def log_density(self, Xnew, Y, obs_cov=None, obs_var=None, grad: bool = False) -> LogDensityResult:
+        """The emulator log-likelihood at the snapshot, one value per row of Xnew (one walker each):
+        ``logp[s] = log N(Y_s | mean(Xnew_s), diag(var(Xnew_s) + obs_var_s) + obs_cov)``, and with
+        ``grad=True`` its exact gradient w.r.t. Xnew, all from one call on the cache block
+        (mfgp_*_posterior_logdens: the predict call's two launches, one density launch that factors the
+        [P, P] covariance of every row in LDS, and k_post_grad fed the density's own gradients; the forward
+        runs once, no [N*, P, P] tensor, no rocSOLVER call, no autograd graph).
+
+        ``Y`` is [P] (one data vector for every row) or [N*, P]; ``obs_var`` a scalar, [P] or [N*, P];
+        ``obs_cov`` [P, P] symmetric positive definite (its lower triangle is read), P <= 128.  Both may
+        be given and are added.  The emulator's own likelihood noise is NOT added: this is the density of
+        f, pass what the data carry in ``obs_var``.  Without ``obs_cov`` the diagonal form runs (any P);
+        there a NaN target is a missing output and is left out.
+
+        Returns ``LogDensityResult(logp [N*], mean [N*, P], var [N*, P], grad_X [N*, D + 1] or None)``,
+        detached; mean / var carry predict_f's bits, grad_X is bitwise ``predict_f_vjp`` fed the density's
+        gradients, its fidelity column exactly 0.  ValueError before any device work for a wrong shape,
+        P > 128 with obs_cov or a negative obs_var; NotImplementedError for a NOCACHE posterior and for
+        ``grad=True`` on the graph model, as predict_f_vjp.  The call's one host read is info, after
+        everything is enqueued: CholeskyError naming the row whose covariance is not positive definite or
+        whose residual is not finite (e.g. a NaN input row)."""
+        what = "log_density"
+        self._need_cache(f"{what}: a NOCACHE posterior has no cached factors; use a TENSOR or VARIABLE cache")
+        if grad:
+            self._check_vjp()
+        p, d = self._num_outputs(), self._input_dim()
+        ns = _design_rows(Xnew, d, f"{what}: Xnew")
+        density_plan(what, ns, p, Y, obs_var, obs_cov)
+        eng = self._engine()   # every ValueError of the arguments is raised above
+        Xs = to_dev(Xnew, eng.device)
+        Yd, ov, oc = density_inputs(eng, p, Y, obs_var, obs_cov)
+        mean, var, logp, gX, info = self._logdens(eng, Xs, Yd, ov, oc, bool(grad))
+        raise_density_info(what, info, oc is not None)
+        return LogDensityResult(as_result(logp), as_result(mean), as_result(var),
+                                None if gX is None else as_result(gX))
+
+    def predict_log_density(self, data, full_cov: bool = False, full_output_cov: bool = False):
+        """GPflow ``GPModel.predict_log_density((Xnew, Ynew))`` on this posterior's marginal predict_f:
+        [N*], summed over the outputs, the model's likelihood variance added (posteriors.predict_log_density_of;
+        the likelihood is not part of the snapshot: it does not enter predict_f).  Either covariance flag
+        raises NotImplementedError, as GPflow does."""
+        return predict_log_density_of(self.model, self.predict_f, data, full_cov, full_output_cov)
+
     def _check_vjp(self):
         pass
 
@@ -587,6 +756,14 @@ class GPRPosterior(_Posterior):
 
     def _num_outputs(self) -> int:
         return self._shape[1]
+
+    def _input_dim(self) -> int:
+        return self._shape[2]
+
+    def _logdens(self, eng, Xs, Y, obs_var, obs_cov, grad):
+        mean, var, logp, gX, info = eng.gpr_posterior_logdens(self._nlf, self._shape, self.cache, Xs, Y, obs_var,
+                                                              obs_cov, grad)
+        return mean, var[:, None].expand(-1, self._shape[1]).contiguous(), logp, gX, info
 
     def _joint(self, eng, Xs):
         """(mean [N*, P], the ONE [1, N*, N*] block, ncol = P): never tiled over P, factored once."""
@@ -762,6 +939,12 @@ class SVGPPosterior(_Posterior):
 
     def _num_outputs(self) -> int:
         return self._shape[2]
+
+    def _input_dim(self) -> int:
+        return self._shape[3]
+
+    def _logdens(self, eng, Xs, Y, obs_var, obs_cov, grad):
+        return eng.svgp_posterior_logdens(self._shape, self.cache, Xs, Y, obs_var, obs_cov, grad)
 
     def _joint(self, eng, Xs):
         """(mean [N*, P], cov [P, N*, N*] of the snapshot, ncol = 1): one factor per output."""

@@ -28,7 +28,8 @@ import torch
 from .engine import Engine, theta_size, to_dev
 from .kernels import LinearCoregionalization, LinearMultiFidelityKernel, SeparateIndependent
 from .models import CholeskyError, Gaussian, HeteroscedasticGaussian, MaskedGaussian
-from .posteriors import DEFAULT_SAMPLE_JITTER, PrecomputeCacheType, SVGPPosterior, draw_f_samples
+from .posteriors import (DEFAULT_SAMPLE_JITTER, PrecomputeCacheType, SVGPPosterior, draw_f_samples,
+                         predict_log_density_of)
 from .params import (Module, Parameter, Softplus, as_result, gather_entries, multiple_assign, parameter_dict,
                      scatter_entries, tie_entries)
 from .session import _PackedAdam, _Session, check_outcome, span_from_tie
@@ -200,6 +201,14 @@ class _SVGPBase(Module):
         if self._masked():
             return mean, as_result(var + to_dev(self._noise_vector(), var.device)[None, :])
         return mean, as_result(var + self._noise())
+
+    def predict_log_density(self, data, full_cov=False, full_output_cov=False):
+        """GPflow GPModel.predict_log_density((Xnew, Ynew)): [N*], summed over the outputs as
+        Gaussian._predict_log_density does (mfgp_mvn_logpdf, the diagonal form).  HeteroscedasticGaussian:
+        the baseline alone for [N*, P] targets, baseline + Y_unc**2 for [N*, 2P] targets [Y_obs | Y_unc];
+        MaskedGaussian: each output's own variance, NaN targets left out.  Either covariance flag raises
+        NotImplementedError."""
+        return predict_log_density_of(self, self.predict_f, data, full_cov, full_output_cov)
 
     def predict_f_samples(self, Xnew, num_samples=None, full_cov: bool = True, full_output_cov: bool = False, *,
                           eps=None, generator=None, jitter: float = DEFAULT_SAMPLE_JITTER):
