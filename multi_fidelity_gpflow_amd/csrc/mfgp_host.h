@@ -4,7 +4,7 @@
 //   mfgp_fence.hip           the device-wide flow fence (mfgp_fence.h) and mfgp_flow_fence
 //   mfgp_gpr_capi.hip        fp64 GPR / graph-kernel training and predict: gpr_layout, gpr_factor
 //   mfgp_f32_capi.hip        the fp32 path, the fp32 settings and the dtype-generic *_ex entries
-//   mfgp_posterior_capi.hip  the cached posterior
+//   mfgp_posterior_capi.hip  the cached posterior: its caches, the workspace chain, the forward drivers
 //   mfgp_density.hip         mfgp_mvn_logpdf, beside its kernels
 #pragma once
 #include <hip/hip_runtime.h>
@@ -111,6 +111,51 @@ static int gpr_check(mfgp_handle_t h, const GprProblemT<T>& P, int lf_min, bool 
 template <class T>
 static bool gpr_predict_io_ok(const GprPredictIOT<T>& io, bool want_cov) {
     return io.Xs && io.mean && io.var && (!want_cov || (io.cov && io.ldc >= io.nstar));
+}
+
+// One cached-posterior call (mfgp_posterior_capi.hip), filled once by its C-ABI entry as a GPR call is:
+// which cache (a size query leaves cache and cache_bytes zero), and the query both families share.  What
+// a query carries beyond the forward selects the call: cov (GPR predict), grad (the VJP call) or dens (the
+// log-density call; with dens->gX the VJP fed the density's own gradients).
+struct GprCacheRef { int nlf, n, p, d; const void* cache; size_t cache_bytes; };
+struct SvgpCacheRef { int m, l, p, d, mixed; const void* cache; size_t cache_bytes; };
+struct PostGradIO {
+    const double* gmean; long ldgm;
+    const double* gvar;
+    double* gX; long ldgx;
+};
+struct LogdensIO {
+    const double* Y; long y_rs;
+    const double* obs_var; long ov_rs;
+    const double* obs_cov; int ldc;
+    double* logp;
+    double* gX; int ldgx;     // nullptr: the value only, the call ends behind the density launch
+    int* info;
+};
+struct PostQuery {
+    int nstar;
+    const double* Xs; int ldxs;
+    void* ws; size_t ws_bytes;
+    double* mean; int ldm;    // SVGP: f_mu [nstar x p], ldm = p
+    double* var;              // GPR [nstar]; SVGP: f_var [nstar x p]
+    double* cov; int ldc;
+    const PostGradIO* grad;
+    const LogdensIO* dens;
+};
+// The posterior entries' argument checks, in gpr_check_dims' order: handle, d (MFGP_ERR_DIM), the family's
+// sizes, then rest_ok; an SVGP cache without a mixing matrix has a latent per output.
+static inline int gpr_post_check(mfgp_handle_t h, const GprCacheRef& c, bool rest_ok) {
+    return gpr_check_dims(h, c.n, c.p, c.d, c.nlf, 0, rest_ok);
+}
+static inline int svgp_post_check(mfgp_handle_t h, const SvgpCacheRef& c, bool rest_ok) {
+    CHECK_H(h);
+    CHECK_D(c.d);
+    if (c.m < 1 || c.l < 1 || c.p < 1 || !rest_ok) return MFGP_ERR_ARG;
+    return !c.mixed && c.l != c.p ? MFGP_ERR_ARG : MFGP_OK;
+}
+// the pointers and leading dimensions every compute entry with a query needs (p outputs, d inputs)
+static inline bool post_query_ok(const PostQuery& q, const void* cache, int p, int d) {
+    return cache && q.Xs && q.ws && q.mean && q.var && q.ldxs >= d + 1 && q.ldm >= p;
 }
 
 // Below this many 32-tiles the launch-per-step Cholesky is faster than the persistent flow (one

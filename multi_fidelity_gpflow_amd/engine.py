@@ -655,28 +655,60 @@ class Engine:
               "mfgp_gpr_posterior_build")
         return info
 
+    def _posterior_run(self, name, key, dims, head, tail):
+        """name(h, *head, ws, ws_bytes, *tail) on the workspace `key`, sized by name_workspace_size(h, *dims)."""
+        h, nbytes = self.h, C.c_size_t(0)
+        check(getattr(self.lib, name + "_workspace_size")(h, *dims, C.byref(nbytes)), name + "_workspace_size")
+        ws = self.workspace(key, nbytes.value)
+        check(getattr(self.lib, name)(h, *head, ptr(ws), ws.numel(), *tail), name)
+
+    # The forward entries (predict, predict_vjp, logdens) of the two families share their shape: the integers
+    # `dims` of their size query first -- GPR (nlf, n, p, d, ns), SVGP (ns, m, L, p, d) -- then `flags` (SVGP:
+    # mixed), the cache, Xs, the workspace, mean (GPR: with its leading dimension), var (GPR [ns], SVGP [ns, p]).
+    def _posterior_predict(self, fam, dims, flags, p, d, cache, Xs, full_cov, grad, out):
+        gpr = fam == "gpr"
+        ns = Xs.shape[0]
+        if out is None:
+            f64 = dict(dtype=torch.float64, device=self.device)
+            third = (ns, d + 1) if grad is not None else (ns, ns) if full_cov else None
+            out = (torch.empty((ns, p), **f64), torch.empty((ns,) if gpr else (ns, p), **f64),
+                   None if third is None else torch.empty(third, **f64))
+        mean, var, third = out
+        if ns == 0:
+            return out
+        head = (*dims, *flags, ptr(cache), cache.numel(), ptr(Xs), Xs.shape[1])
+        outs = (ptr(mean), p, ptr(var)) if gpr else (ptr(mean), ptr(var))
+        # the two entries share their arguments up to var; then (GPR) cov, ldc / gmean, ldgm, gvar, gX, ldgx
+        if grad is None:
+            self._posterior_run(f"mfgp_{fam}_posterior_predict", "post_pred", dims, head,
+                                outs + (ptr(third), ns) if gpr else outs)
+        else:
+            self._posterior_run(f"mfgp_{fam}_posterior_predict_vjp", "post_vjp", dims, head,
+                                outs + (ptr(grad[0]), p, ptr(grad[1]), ptr(third), d + 1))
+        return out
+
+    def _posterior_logdens(self, fam, dims, flags, p, d, cache, Xs, Y, obs_var, obs_cov, grad):
+        gpr = fam == "gpr"
+        ns = Xs.shape[0]
+        f64 = dict(dtype=torch.float64, device=self.device)
+        mean, var = torch.empty((ns, p), **f64), torch.empty((ns,) if gpr else (ns, p), **f64)
+        logp = torch.empty((ns,), **f64)
+        gX = torch.empty((ns, d + 1), **f64) if grad else None
+        info = torch.zeros((ns,), dtype=torch.int32, device=self.device)
+        keep, dargs = self._density_args("log_density", ns, p, Y, obs_var, obs_cov)
+        if ns:
+            head = (*dims, *flags, ptr(cache), cache.numel(), ptr(Xs), Xs.shape[1])
+            outs = (ptr(mean), p, ptr(var)) if gpr else (ptr(mean), ptr(var))
+            self._posterior_run(f"mfgp_{fam}_posterior_logdens", "post_logdens", dims, head,
+                                (*outs, *dargs, ptr(logp), ptr(gX), d + 1, ptr(info)))
+        return mean, var, logp, gX, info
+
     def gpr_posterior_predict(self, nlf, shape, cache, Xs, full_cov=False, grad=None, out=None):
         """(mean [ns, p], var [ns], third): third is cov [ns, ns] with full_cov, else None.  grad =
         (grad_mean [ns, p], grad_var [ns]), either may be None (zero): the VJP call, third is the gradient
         w.r.t. Xs [ns, d + 1].  out: the three result tensors, preallocated."""
         n, p, d = shape
-        ns = Xs.shape[0]
-        if out is None:
-            f64 = dict(dtype=torch.float64, device=self.device)
-            third = (ns, d + 1) if grad is not None else (ns, ns) if full_cov else None
-            out = (torch.empty((ns, p), **f64), torch.empty((ns,), **f64),
-                   None if third is None else torch.empty(third, **f64))
-        mean, var, third = out
-        if ns == 0:
-            return out
-        # the two entries share their arguments up to var; then cov, ldc / gmean, ldgm, gvar, gX, ldgx
-        name = "mfgp_gpr_posterior_predict" if grad is None else "mfgp_gpr_posterior_predict_vjp"
-        tail = (ptr(third), ns) if grad is None else (ptr(grad[0]), p, ptr(grad[1]), ptr(third), d + 1)
-        ws = self.workspace("post_pred" if grad is None else "post_vjp",
-                            self._size(getattr(self.lib, name + "_workspace_size"), nlf, n, p, d, ns))
-        check(getattr(self.lib, name)(self.h, nlf, n, p, d, ns, ptr(cache), cache.numel(), ptr(Xs), Xs.shape[1],
-                                      ptr(ws), ws.numel(), ptr(mean), p, ptr(var), *tail), name)
-        return out
+        return self._posterior_predict("gpr", (nlf, n, p, d, Xs.shape[0]), (), p, d, cache, Xs, full_cov, grad, out)
 
     def gpr_posterior_leave_out(self, nlf, shape, cache, offsets, rows, gmax, out=None):
         """Leave-group-out from the cache: int32 device offsets [G + 1] and rows [R] (group g is
@@ -689,11 +721,9 @@ class Engine:
             out = (torch.empty((nr, p), **f64), torch.empty((nr, gmax), **f64), torch.empty((ng, p), **f64),
                    torch.empty((ng,), dtype=torch.int32, device=self.device))
         resid, cov, logd, info = out
-        ws = self.workspace("post_lo", self._size(self.lib.mfgp_gpr_posterior_leave_out_workspace_size, nlf, n, p, d,
-                                                  ng, nr))
-        check(self.lib.mfgp_gpr_posterior_leave_out(self.h, nlf, n, p, d, ptr(cache), cache.numel(), ng, ptr(offsets),
-                                                    ptr(rows), nr, gmax, ptr(ws), ws.numel(), ptr(resid), p, ptr(cov),
-                                                    gmax, ptr(logd), ptr(info)), "mfgp_gpr_posterior_leave_out")
+        self._posterior_run("mfgp_gpr_posterior_leave_out", "post_lo", (nlf, n, p, d, ng, nr),
+                            (nlf, n, p, d, ptr(cache), cache.numel(), ng, ptr(offsets), ptr(rows), nr, gmax),
+                            (ptr(resid), p, ptr(cov), gmax, ptr(logd), ptr(info)))
         return out
 
     def gpr_posterior_design_workspace(self, nlf, shape, nref, ncand, qmax) -> torch.Tensor:
@@ -730,12 +760,9 @@ class Engine:
         k = Xadd.shape[0]
         mean = torch.empty((k, p), dtype=torch.float64, device=self.device)
         info = torch.empty((1,), dtype=torch.int32, device=self.device)
-        ws = self.workspace("post_append", self._size(self.lib.mfgp_gpr_posterior_append_workspace_size, nlf, n, p, d,
-                                                      k))
-        check(self.lib.mfgp_gpr_posterior_append(self.h, nlf, n, p, d, k, ptr(cache), cache.numel(), ptr(Xadd),
-                                                 Xadd.shape[1], ptr(Yadd), p, ptr(ws), ws.numel(), ptr(out_cache),
-                                                 out_cache.numel(), ptr(mean), p, ptr(info)),
-              "mfgp_gpr_posterior_append")
+        self._posterior_run("mfgp_gpr_posterior_append", "post_append", (nlf, n, p, d, k),
+                            (nlf, n, p, d, k, ptr(cache), cache.numel(), ptr(Xadd), Xadd.shape[1], ptr(Yadd), p),
+                            (ptr(out_cache), out_cache.numel(), ptr(mean), p, ptr(info)))
         return mean, info
 
     def svgp_posterior_bytes(self, m, L, p, d) -> int:
@@ -756,58 +783,22 @@ class Engine:
         """(f_mu [ns, p], f_var [ns, p], None); grad = (grad_mean, grad_var), each [ns, p] or None (zero):
         the VJP call, third is the gradient w.r.t. Xs [ns, d + 1]."""
         m, L, p, d, mixed = shape
-        ns = Xs.shape[0]
-        f64 = dict(dtype=torch.float64, device=self.device)
-        f_mu, f_var = torch.empty((ns, p), **f64), torch.empty((ns, p), **f64)
-        gX = None if grad is None else torch.empty((ns, d + 1), **f64)
-        if ns == 0:
-            return f_mu, f_var, gX
-        name = "mfgp_svgp_posterior_predict" if grad is None else "mfgp_svgp_posterior_predict_vjp"
-        tail = () if grad is None else (ptr(grad[0]), p, ptr(grad[1]), ptr(gX), d + 1)
-        ws = self.workspace("post_pred" if grad is None else "post_vjp",
-                            self._size(getattr(self.lib, name + "_workspace_size"), ns, m, L, p, d))
-        check(getattr(self.lib, name)(self.h, ns, m, L, p, d, 1 if mixed else 0, ptr(cache), cache.numel(), ptr(Xs),
-                                      Xs.shape[1], ptr(ws), ws.numel(), ptr(f_mu), ptr(f_var), *tail), name)
-        return f_mu, f_var, gX
+        return self._posterior_predict("svgp", (Xs.shape[0], m, L, p, d), (1 if mixed else 0,), p, d, cache, Xs,
+                                       False, grad, None)
 
     def gpr_posterior_logdens(self, nlf, shape, cache, Xs, Y, obs_var=None, obs_cov=None, grad=False):
         """mfgp_gpr_posterior_logdens: the forward, the density launch and (grad) k_post_grad in one call ->
         (mean [ns, p], var [ns], logp [ns], grad_X [ns, d + 1] or None, info [ns] int32).  Y / obs_var /
         obs_cov as _density_args.  No host read of a device word."""
         n, p, d = shape
-        ns = Xs.shape[0]
-        f64 = dict(dtype=torch.float64, device=self.device)
-        mean, var, logp = torch.empty((ns, p), **f64), torch.empty((ns,), **f64), torch.empty((ns,), **f64)
-        gX = torch.empty((ns, d + 1), **f64) if grad else None
-        info = torch.zeros((ns,), dtype=torch.int32, device=self.device)
-        keep, dargs = self._density_args("log_density", ns, p, Y, obs_var, obs_cov)
-        if ns == 0:
-            return mean, var, logp, gX, info
-        ws = self.workspace("post_logdens", self._size(self.lib.mfgp_gpr_posterior_logdens_workspace_size, nlf, n, p,
-                                                       d, ns))
-        check(self.lib.mfgp_gpr_posterior_logdens(self.h, nlf, n, p, d, ns, ptr(cache), cache.numel(), ptr(Xs),
-                                                  Xs.shape[1], ptr(ws), ws.numel(), ptr(mean), p, ptr(var), *dargs,
-                                                  ptr(logp), ptr(gX), d + 1, ptr(info)), "mfgp_gpr_posterior_logdens")
-        return mean, var, logp, gX, info
+        return self._posterior_logdens("gpr", (nlf, n, p, d, Xs.shape[0]), (), p, d, cache, Xs, Y, obs_var, obs_cov,
+                                       grad)
 
     def svgp_posterior_logdens(self, shape, cache, Xs, Y, obs_var=None, obs_cov=None, grad=False):
         """mfgp_svgp_posterior_logdens -> (f_mu [ns, p], f_var [ns, p], logp [ns], grad_X or None, info [ns])."""
         m, L, p, d, mixed = shape
-        ns = Xs.shape[0]
-        f64 = dict(dtype=torch.float64, device=self.device)
-        f_mu, f_var, logp = torch.empty((ns, p), **f64), torch.empty((ns, p), **f64), torch.empty((ns,), **f64)
-        gX = torch.empty((ns, d + 1), **f64) if grad else None
-        info = torch.zeros((ns,), dtype=torch.int32, device=self.device)
-        keep, dargs = self._density_args("log_density", ns, p, Y, obs_var, obs_cov)
-        if ns == 0:
-            return f_mu, f_var, logp, gX, info
-        ws = self.workspace("post_logdens", self._size(self.lib.mfgp_svgp_posterior_logdens_workspace_size, ns, m, L,
-                                                       p, d))
-        check(self.lib.mfgp_svgp_posterior_logdens(self.h, ns, m, L, p, d, 1 if mixed else 0, ptr(cache),
-                                                   cache.numel(), ptr(Xs), Xs.shape[1], ptr(ws), ws.numel(), ptr(f_mu),
-                                                   ptr(f_var), *dargs, ptr(logp), ptr(gX), d + 1, ptr(info)),
-              "mfgp_svgp_posterior_logdens")
-        return f_mu, f_var, logp, gX, info
+        return self._posterior_logdens("svgp", (Xs.shape[0], m, L, p, d), (1 if mixed else 0,), p, d, cache, Xs, Y,
+                                       obs_var, obs_cov, grad)
 
     def selftest_mfma(self) -> np.ndarray:
         out = torch.zeros((16, 16), dtype=torch.float64, device=self.device)
