@@ -293,6 +293,36 @@ int mfgp_mvn_logpdf(mfgp_handle_t h, int ns, int p, const double* mean, int ldm,
                     const double* obs_cov, int ldc, void* ws, size_t ws_bytes, double* logp, double* gmean, int ldgm,
                     double* gvar, int ldgv, int* info /* [ns] */);
 
+/* Batched Fisher (Gauss-Newton) matrix of an emulated data vector: per row s < ns, with Sigma_s as in
+ * mfgp_mvn_logpdf and J_s [p x d] the Jacobian of the mean w.r.t. the d inputs,
+ *   F[s] = J_s^T Sigma_s^{-1} J_s                          [d x d], exactly symmetric.
+ *   J        [ns][d][ldj], ldj >= p: J[s][k][c] = d mean(s, c) / d x(s, k), outputs fastest -- the layout the
+ *            mfgp_*_jacobian entries write.
+ *   var / obs_var / obs_cov  addressed as mfgp_mvn_logpdf addresses them (var_cs = 0: one variance per row).
+ *   F        [ns][d][d], dense.
+ *   info     [ns]: 0, or the 1-based index of the first output with a non-positive / non-finite pivot (dense
+ *            form) or total variance (diagonal form); that row's F is then unspecified, the others unaffected.
+ * Dense form (obs_cov given): one workgroup per row.  Sigma_s is formed in LDS as mfgp_mvn_logpdf forms it,
+ * the d rows of J_s^T are put under it and the 8-column block Cholesky carries them along: they become
+ * J^T L^{-T} and their own trailing updates leave -F[s] in the d x d corner, so F costs no pass of its own;
+ * the corner's lower triangle is negated and mirrored.  The LDS image is (P8 + d) x ((P8 + d) | 1) doubles,
+ * P8 = p rounded up to 8, chosen at launch (44.4 KB at p = 64, d = 10).  Limit: p <= 128 AND the image within
+ * the 160 KiB of a compute unit, i.e. P8 + d <= 143 (p = 128: d <= 15; p <= 104: any d <= 32); beyond it
+ * MFGP_ERR_ARG -- use the diagonal form.  Diagonal form (obs_cov NULL): any p,
+ * F[a][b] = sum_c J[c][a] J[c][b] / (var_c + obs_var_c) in output order.  One launch either way; fixed-order
+ * sums, no floating-point atomics: a row's bits do not depend on ns or on the other rows.  Nothing is
+ * allocated, no synchronisation, no host read of a device word; the workspace is reserved
+ * (mfgp_mvn_fisher_workspace_size).  ns = 0: a no-op (MFGP_OK, decided before the pointers are looked at).
+ * d outside 1..MFGP_MAX_D: MFGP_ERR_DIM; a negative count, p < 1, a short leading dimension or stride, or a
+ * null required pointer: MFGP_ERR_ARG; a short workspace: MFGP_ERR_WORKSPACE; all before any device work.
+ * This is the mean term of the Gaussian Fisher information; the 1/2 tr(Sigma^-1 dSigma Sigma^-1 dSigma) term
+ * of a variance that depends on x is not formed.
+ * Replaces: d one-hot VJPs + torch.linalg.cholesky / cholesky_solve on an [ns, p, p] batch. */
+int mfgp_mvn_fisher_workspace_size(mfgp_handle_t h, int ns, int p, int d, size_t* bytes);
+int mfgp_mvn_fisher(mfgp_handle_t h, int ns, int p, int d, const double* J, int ldj, const double* var, long var_rs,
+                    long var_cs, const double* obs_var, long ov_rs, const double* obs_cov, int ldc, void* ws,
+                    size_t ws_bytes, double* F, int* info /* [ns] */);
+
 /* SVGP ELBO value (GPflow SVGP.elbo, whiten=True, Gaussian likelihood) for the
  * latent LinearCoregionalization model (mfgpflow/linear_svgp.py:64-203) and the
  * SingleBinSVGP (SeparateIndependent, mfgpflow/singlebin_svgp.py:13-97, W = I):
@@ -515,6 +545,49 @@ int mfgp_svgp_posterior_logdens(mfgp_handle_t h, int nstar, int m, int l, int p,
                                 double* f_mu, double* f_var, const double* Y, long y_rs, const double* obs_var,
                                 long ov_rs, const double* obs_cov, int ldc, double* logp, double* gX, int ldgx,
                                 int* info);
+
+/* Emulator Jacobian from the cached posterior: J[s][k][c] = d mean(Xs_s)[c] / d Xs[s][k] over the d input
+ * columns (the fidelity column enters only through exact == 0 / == 1 tests and has no slot), linear
+ * multi-fidelity kernel.  With wL = cL vL kL and wD = cD vD kD the two terms of the kernel entry
+ * (cL = 1 | rho | rho^2, cD = 1 for HF x HF):
+ *   GPR   alpha = L^{-T} Z [n x p];   J[s][k][c] = sum_i alpha[i][c] (wL(i, s) / lL_k^2 + wD(i, s) / lD_k^2)
+ *                                                  (x[i][k] - Xs[s][k])
+ *   SVGP  alpha_l = Lm_l^{-T} q_mu[:, l];  dg_l[s][k] the same sum with alpha_l and latent l's parameters;
+ *         J[s][k][c] = sum_l W[c][l] dg_l[s][k] in latent order (mixed = 0: J[s][k][l] = dg_l[s][k]).
+ * A row of either side whose fidelity is neither 0 nor 1 contributes exactly 0.
+ *   *_jacobian_weights  computes alpha from the cache block into `weights` (one launch: a transposed-
+ *            triangular tile product on the matrix core).  It depends on the cache block alone: compute it
+ *            once per block and pass it to every Jacobian call; recompute it whenever the block is rebuilt.
+ *            *_jacobian_weights_workspace_size reports the bytes of `weights` (GPR: Npad x Ppad doubles;
+ *            SVGP: l x Mpad); the call needs no other workspace.  The cache block is not written.
+ *   *_jacobian  arguments as the predict calls (GPR: no cov) plus the weights and J [nstar][d][ldj], ldj >= p,
+ *            outputs fastest (the layout mfgp_mvn_fisher reads).  Enqueues the predict calls' own forward
+ *            (mean / var, f_mu / f_var carry the predict calls' bits), then GPR: one memset of the task
+ *            counters and one launch -- per (column tile of Xs, output tile, chunk of row tiles, group of
+ *            input dimensions) the wL / wD tiles are generated in LDS, G_k = (wL / lL_k^2 + wD / lD_k^2)
+ *            (x_ik - Xs_sk) is formed as the matrix core's operand and acc_k += G_k^T alpha_tile; chunk partials
+ *            are summed in chunk order by the last workgroup to arrive (no spin-wait); SVGP: one launch for the
+ *            latents' dg_l partials, one that sums the chunks (more than one chunk only), one that mixes.
+ *            The chunk count depends on the shapes alone, every sum has a fixed order and there are no
+ *            floating-point atomics: two calls with the same inputs return the same bits.
+ * Workspace: the *_jacobian_workspace_size calls.  A cache, weights buffer or workspace smaller than the size
+ * calls report: MFGP_ERR_WORKSPACE; argument errors MFGP_ERR_ARG / MFGP_ERR_DIM; both before any device work.
+ * Nothing is allocated, the host reads no device word; nstar = 0 is a no-op.  The graph kernel (nlf > 0) is
+ * not supported: MFGP_ERR_ARG.  Use the cache and the weights at the tile size they were built for. */
+int mfgp_gpr_jacobian_weights_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, size_t* bytes);
+int mfgp_gpr_jacobian_weights(mfgp_handle_t h, int nlf, int n, int p, int d, const void* cache, size_t cache_bytes,
+                              void* weights, size_t weights_bytes);
+int mfgp_gpr_jacobian_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar, size_t* bytes);
+int mfgp_gpr_jacobian(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar, const void* cache, size_t cache_bytes,
+                      const void* weights, size_t weights_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes,
+                      double* mean, int ldm, double* var, double* J, int ldj);
+int mfgp_svgp_jacobian_weights_workspace_size(mfgp_handle_t h, int m, int l, int p, int d, size_t* bytes);
+int mfgp_svgp_jacobian_weights(mfgp_handle_t h, int m, int l, int p, int d, int mixed, const void* cache,
+                               size_t cache_bytes, void* weights, size_t weights_bytes);
+int mfgp_svgp_jacobian_workspace_size(mfgp_handle_t h, int nstar, int m, int l, int p, int d, size_t* bytes);
+int mfgp_svgp_jacobian(mfgp_handle_t h, int nstar, int m, int l, int p, int d, int mixed, const void* cache,
+                       size_t cache_bytes, const void* weights, size_t weights_bytes, const double* Xs, int ldxs,
+                       void* ws, size_t ws_bytes, double* f_mu, double* f_var, double* J, int ldj);
 
 /* Leave-group-out cross-validation from a GPR cache, at the cache's hyper-parameters: for each group
  * S of training rows, what a model built without those rows predicts for them, in closed form from

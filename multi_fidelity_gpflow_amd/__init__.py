@@ -19,7 +19,7 @@ from .data import PowerSpecs, map_to_unit_cube, input_normalize  # noqa: F401
 from . import data  # noqa: F401
 from ._lib import MFGPError  # noqa: F401
 from .posteriors import (PrecomputeCacheType, GPRPosterior, SVGPPosterior, LeaveOutResult,  # noqa: F401
-                         DesignResult, LogDensityResult, groups_by_input)
+                         DesignResult, LogDensityResult, FisherResult, groups_by_input)
 from . import posteriors  # noqa: F401
 
 __version__ = "0.1.0"

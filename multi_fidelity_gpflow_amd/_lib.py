@@ -110,6 +110,16 @@ SIGNATURES = {
     "mfgp_svgp_posterior_logdens_workspace_size": [_p, _i, _i, _i, _i, _i, C.POINTER(_sz)],
     "mfgp_svgp_posterior_logdens": [_p, _i, _i, _i, _i, _i, _i, _p, _sz, _p, _i, _p, _sz, _p, _p, _p, _l, _p, _l, _p,
                                     _i, _p, _p, _i, _p],
+    "mfgp_mvn_fisher_workspace_size": [_p, _i, _i, _i, C.POINTER(_sz)],
+    "mfgp_mvn_fisher": [_p, _i, _i, _i, _p, _i, _p, _l, _l, _p, _l, _p, _i, _p, _sz, _p, _p],
+    "mfgp_gpr_jacobian_weights_workspace_size": [_p, _i, _i, _i, _i, C.POINTER(_sz)],
+    "mfgp_gpr_jacobian_weights": [_p, _i, _i, _i, _i, _p, _sz, _p, _sz],
+    "mfgp_gpr_jacobian_workspace_size": [_p, _i, _i, _i, _i, _i, C.POINTER(_sz)],
+    "mfgp_gpr_jacobian": [_p, _i, _i, _i, _i, _i, _p, _sz, _p, _sz, _p, _i, _p, _sz, _p, _i, _p, _p, _i],
+    "mfgp_svgp_jacobian_weights_workspace_size": [_p, _i, _i, _i, _i, C.POINTER(_sz)],
+    "mfgp_svgp_jacobian_weights": [_p, _i, _i, _i, _i, _i, _p, _sz, _p, _sz],
+    "mfgp_svgp_jacobian_workspace_size": [_p, _i, _i, _i, _i, _i, C.POINTER(_sz)],
+    "mfgp_svgp_jacobian": [_p, _i, _i, _i, _i, _i, _i, _p, _sz, _p, _sz, _p, _i, _p, _sz, _p, _p, _p, _i],
     "mfgp_gpr_posterior_leave_out_workspace_size": [_p, _i, _i, _i, _i, _i, _i, C.POINTER(_sz)],
     "mfgp_gpr_posterior_leave_out": [_p, _i, _i, _i, _i, _p, _sz, _i, _p, _p, _i, _i, _p, _sz, _p, _i, _p, _i, _p,
                                      _p],

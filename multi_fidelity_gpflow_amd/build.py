@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 SOURCES = ["mfgp_kernels.hip", "mfgp_flow.hip", "mfgp_capi.hip", "mfgp_svgp.hip", "mfgp_svgp_grad.hip", "mfgp_f32.hip",
            "mfgp_posterior.hip", "mfgp_leave_out.hip", "mfgp_design.hip", "mfgp_append.hip",
-           "mfgp_posterior_capi.hip", "mfgp_sample.hip", "mfgp_density.hip", "mfgp_gpr_capi.hip", "mfgp_f32_capi.hip", "mfgp_fence.hip"]
+           "mfgp_jacobian.hip", "mfgp_posterior_capi.hip", "mfgp_sample.hip", "mfgp_density.hip", "mfgp_gpr_capi.hip", "mfgp_f32_capi.hip", "mfgp_fence.hip"]
 OUT = os.path.join(HERE, "libmfgp.so")
 
 

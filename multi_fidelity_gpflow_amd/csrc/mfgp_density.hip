@@ -1,4 +1,5 @@
-// Batched Gaussian log-density with its gradients (include/mfgp.h mfgp_mvn_logpdf): per row s,
+// Batched Gaussian log-density with its gradients (include/mfgp.h mfgp_mvn_logpdf) and, on the same covariance
+// and the same LDS factorization, the batched Fisher matrix (mfgp_mvn_fisher, further down): per row s,
 //   Sigma_s = obs_cov + diag(var_s + obs_var_s),  r = y_s - mean_s,
 //   logp_s  = -1/2 r^T Sigma_s^{-1} r - 1/2 log det Sigma_s - (P / 2) log 2 pi,
 //   gmean_s = a = Sigma_s^{-1} r,  gvar_s[c] = 1/2 (a_c^2 - (Sigma_s^{-1})_cc).
@@ -301,6 +302,119 @@ __global__ __launch_bounds__(NTHREADS) void k_mvn_diag(LogpdfArgs a) {
     }
 }
 
+// ---------------------------------------------------------------- Fisher matrix (mfgp_mvn_fisher)
+// F_s = J_s^T Sigma_s^{-1} J_s, Sigma_s as above, J_s [P x D] read from the Jacobian's device layout
+// J[s][k][c] (row k of J_s^T, outputs fastest).
+//   k_fisher_dense  (obs_cov given) one workgroup per row.  The LDS image is (P8 + D) rows of stride
+//                   (P8 + D) | 1 doubles: the lower triangle of Sigma_s exactly as k_mvn_dense builds it, and the
+//                   D rows of J_s^T under it, their last D columns zero.  dense_potrf carries those rows along:
+//                   they become J^T L^{-T}, and their own trailing updates leave -J^T Sigma^{-1} J in the
+//                   D x D corner, so the Fisher matrix costs no pass of its own.  The lower triangle of the
+//                   corner is negated and mirrored: F is exactly symmetric.  The LDS size is chosen at launch
+//                   (fisher_dense_smem): 44.4 KB at P = 64, D = 10; the image must fit the 160 KiB of a CU.
+//   k_fisher_diag   (obs_cov == NULL, any P) one workgroup per row, outputs staged 64 at a time; a thread
+//                   owns up to three (a, b <= a) pairs and adds J[c][a] J[c][b] / (var_c + ov_c) in output order.
+// A row reads nothing of another row: its bits do not depend on ns or on its neighbours.  info[s] is the
+// 1-based index of the first output with a non-positive / non-finite pivot (dense) or total variance
+// (diagonal), 0 if none.
+constexpr int FISHER_MAXD = 32;
+constexpr int FISHER_PAIRS = (FISHER_MAXD * (FISHER_MAXD + 1) / 2 + NTHREADS - 1) / NTHREADS;
+
+__global__ __launch_bounds__(NTHREADS) void k_fisher_dense(FisherArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int t = threadIdx.x;
+    const long s = blockIdx.x;
+    const int P = a.p, D = a.d, n8 = mvn_p8(P), R = n8 + D, S = R | 1;
+    double* __restrict__ A = smem;
+    const double* __restrict__ vp = a.var + s * a.var_rs;
+    const double* __restrict__ op = a.obs_var ? a.obs_var + s * a.ov_rs : nullptr;
+    for (int e = t; e < n8 * n8; e += NTHREADS) {
+        const int i = e / n8, j = e - i * n8;
+        if (j > i) continue;
+        double v;
+        if (i < P) {
+            v = a.obs_cov[(long)i * a.ldc + j];
+            if (i == j) v += vp[(long)i * a.var_cs] + (op ? op[i] : 0.0);
+        } else {
+            v = i == j ? 1.0 : 0.0;   // beyond P: an identity block
+        }
+        A[i * S + j] = v;
+    }
+    const double* __restrict__ Jp = a.J + s * D * a.ldj;
+    for (int e = t; e < D * R; e += NTHREADS) {
+        const int k = e / R, c = e - k * R;
+        A[(n8 + k) * S + c] = c < P ? Jp[(long)k * a.ldj + c] : 0.0;   // (c >= n8: the corner that collects -F)
+    }
+    __syncthreads();
+    const int bad = dense_potrf(A, n8, S, D);
+    double* __restrict__ Fp = a.F + s * D * D;
+    for (int e = t; e < D * D; e += NTHREADS) {
+        const int i = e / D, j = e - i * D;
+        const int lo = i > j ? i : j, hi = i > j ? j : i;
+        Fp[e] = 0.0 - A[(n8 + lo) * S + n8 + hi];
+    }
+    if (t == 0) a.info[s] = bad;
+}
+
+__global__ __launch_bounds__(NTHREADS) void k_fisher_diag(FisherArgs a) {
+    __shared__ double Js[FISHER_MAXD][65];
+    __shared__ double wv[64];
+    __shared__ int sbad;
+    const int t = threadIdx.x;
+    const long s = blockIdx.x;
+    const int P = a.p, D = a.d, npair = D * (D + 1) / 2;
+    const double* __restrict__ vp = a.var + s * a.var_rs;
+    const double* __restrict__ op = a.obs_var ? a.obs_var + s * a.ov_rs : nullptr;
+    const double* __restrict__ Jp = a.J + s * D * a.ldj;
+    if (t == 0) sbad = 0x7fffffff;
+    int pa[FISHER_PAIRS], pb[FISHER_PAIRS];
+    double acc[FISHER_PAIRS];
+#pragma unroll
+    for (int u = 0; u < FISHER_PAIRS; ++u) {   // pair e -> (a, b <= a), row by row of the lower triangle
+        int e = t + u * NTHREADS, i = 0;
+        if (e >= npair) e = 0;
+        while (e > i) { e -= i + 1; ++i; }
+        pa[u] = i;
+        pb[u] = e;
+        acc[u] = 0.0;
+    }
+    for (int c0 = 0; c0 < P; c0 += 64) {
+        __syncthreads();   // the previous block's readers (first block: sbad is initialised)
+        for (int e = t; e < D * 64; e += NTHREADS) {
+            const int k = e >> 6, c = c0 + (e & 63);
+            Js[k][e & 63] = c < P ? Jp[(long)k * a.ldj + c] : 0.0;
+        }
+        if (t < 64) {
+            const int c = c0 + t;
+            double w = 0.0;
+            if (c < P) {
+                const double v = vp[(long)c * a.var_cs] + (op ? op[c] : 0.0);
+                if (!(v > 0.0 && v < INFINITY)) atomicMin(&sbad, c + 1);
+                w = 1.0 / v;
+            }
+            wv[t] = w;
+        }
+        __syncthreads();
+        const int nc = P - c0 < 64 ? P - c0 : 64;
+#pragma unroll
+        for (int u = 0; u < FISHER_PAIRS; ++u) {
+            if (t + u * NTHREADS >= npair) continue;
+            double v = acc[u];
+            for (int c = 0; c < nc; ++c) v += Js[pa[u]][c] * Js[pb[u]][c] * wv[c];
+            acc[u] = v;
+        }
+    }
+    double* __restrict__ Fp = a.F + s * D * D;
+#pragma unroll
+    for (int u = 0; u < FISHER_PAIRS; ++u) {
+        if (t + u * NTHREADS >= npair) continue;
+        Fp[pa[u] * D + pb[u]] = acc[u];
+        Fp[pb[u] * D + pa[u]] = acc[u];
+    }
+    __syncthreads();
+    if (t == 0) a.info[s] = sbad == 0x7fffffff ? 0 : sbad;
+}
+
 }  // namespace
 
 void launch_mvn_logpdf(const LogpdfArgs& a, hipStream_t s) {
@@ -323,6 +437,34 @@ bool mvn_logpdf_geometry_ok(int ns, int p, bool dense, int ldc, long y_rs, long 
     if (ns < 0 || p < 1 || y_rs < 0 || ov_rs < 0) return false;
     if (dense && (p > MVN_DENSE_MAXP || ldc < p)) return false;
     return (y_rs == 0 || y_rs >= p) && (ov_rs == 0 || ov_rs >= p);
+}
+
+// the dense Fisher kernel's LDS: the (P8 + D) x ((P8 + D) | 1) image
+size_t fisher_dense_smem(int p, int d) {
+    const size_t r = (size_t)mvn_p8(p) + (size_t)d;
+    return r * (r | 1) * sizeof(double);
+}
+
+void launch_mvn_fisher(const FisherArgs& a, hipStream_t s) {
+    if (a.ns <= 0) return;
+    if (a.obs_cov) {
+        static bool attr = false;
+        if (!attr) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fisher_dense),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)FISHER_LDS_BYTES);
+            attr = true;
+        }
+        hipLaunchKernelGGL(k_fisher_dense, dim3((unsigned)a.ns), dim3(NTHREADS), fisher_dense_smem(a.p, a.d), s, a);
+    } else {
+        hipLaunchKernelGGL(k_fisher_diag, dim3((unsigned)a.ns), dim3(NTHREADS), 0, s, a);
+    }
+}
+
+// the argument test of mfgp_mvn_fisher; dense: P <= 128 and the image within the LDS of a CU
+bool mvn_fisher_geometry_ok(int ns, int p, int d, bool dense, int ldc, long ov_rs) {
+    if (ns < 0 || p < 1 || d < 1 || d > FISHER_MAXD || ov_rs < 0) return false;
+    if (dense && (p > MVN_DENSE_MAXP || ldc < p || fisher_dense_smem(p, d) > FISHER_LDS_BYTES)) return false;
+    return ov_rs == 0 || ov_rs >= p;
 }
 
 }  // namespace mfgp
@@ -361,6 +503,36 @@ int mfgp_mvn_logpdf(mfgp_handle_t h, int ns, int p, const double* mean, int ldm,
     a.logp = logp; a.gmean = gmean; a.ldgm = ldgm; a.gvar = gvar; a.ldgv = ldgv; a.gv_sum = gv_sum ? 1 : 0;
     a.info = info;
     launch_mvn_logpdf(a, h->stream);
+    return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
+}
+
+int mfgp_mvn_fisher_workspace_size(mfgp_handle_t h, int ns, int p, int d, size_t* bytes) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (ns < 0 || p < 1 || !bytes) return MFGP_ERR_ARG;
+    *bytes = MVN_FISHER_WS_BYTES;
+    return MFGP_OK;
+}
+
+int mfgp_mvn_fisher(mfgp_handle_t h, int ns, int p, int d, const double* J, int ldj, const double* var, long var_rs,
+                    long var_cs, const double* obs_var, long ov_rs, const double* obs_cov, int ldc, void* ws,
+                    size_t ws_bytes, double* F, int* info) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (!mvn_fisher_geometry_ok(ns, p, d, obs_cov != nullptr, ldc, ov_rs) || ldj < p || var_rs < 0 ||
+        (var_cs != 0 && var_cs != 1))
+        return MFGP_ERR_ARG;
+    if (ns == 0) return MFGP_OK;
+    if (!J || !var || !ws || !F || !info) return MFGP_ERR_ARG;
+    if (ws_bytes < MVN_FISHER_WS_BYTES) return MFGP_ERR_WORKSPACE;
+    FisherArgs a{};
+    a.ns = ns; a.p = p; a.d = d;
+    a.J = J; a.ldj = ldj;
+    a.var = var; a.var_rs = var_rs; a.var_cs = var_cs;
+    a.obs_var = obs_var; a.ov_rs = ov_rs;
+    a.obs_cov = obs_cov; a.ldc = ldc;
+    a.F = F; a.info = info;
+    launch_mvn_fisher(a, h->stream);
     return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
 }
 

@@ -5,7 +5,7 @@
 //   mfgp_gpr_capi.hip        fp64 GPR / graph-kernel training and predict: gpr_layout, gpr_factor
 //   mfgp_f32_capi.hip        the fp32 path, the fp32 settings and the dtype-generic *_ex entries
 //   mfgp_posterior_capi.hip  the cached posterior: its caches, the workspace chain, the forward drivers
-//   mfgp_density.hip         mfgp_mvn_logpdf, beside its kernels
+//   mfgp_density.hip         mfgp_mvn_logpdf and mfgp_mvn_fisher, beside their kernels
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -115,8 +115,8 @@ static bool gpr_predict_io_ok(const GprPredictIOT<T>& io, bool want_cov) {
 
 // One cached-posterior call (mfgp_posterior_capi.hip), filled once by its C-ABI entry as a GPR call is:
 // which cache (a size query leaves cache and cache_bytes zero), and the query both families share.  What
-// a query carries beyond the forward selects the call: cov (GPR predict), grad (the VJP call) or dens (the
-// log-density call; with dens->gX the VJP fed the density's own gradients).
+// a query carries beyond the forward selects the call: cov (GPR predict), grad (the VJP call), dens (the
+// log-density call; with dens->gX the VJP fed the density's own gradients) or jac (the Jacobian call).
 struct GprCacheRef { int nlf, n, p, d; const void* cache; size_t cache_bytes; };
 struct SvgpCacheRef { int m, l, p, d, mixed; const void* cache; size_t cache_bytes; };
 struct PostGradIO {
@@ -132,6 +132,10 @@ struct LogdensIO {
     double* gX; int ldgx;     // nullptr: the value only, the call ends behind the density launch
     int* info;
 };
+struct JacIO {
+    const void* weights; size_t weights_bytes;   // alpha = L^{-T} Z / Lm^{-T} q_mu (mfgp_*_jacobian_weights)
+    double* J; long ldj;                         // [nstar][d][ldj], outputs fastest
+};
 struct PostQuery {
     int nstar;
     const double* Xs; int ldxs;
@@ -141,6 +145,7 @@ struct PostQuery {
     double* cov; int ldc;
     const PostGradIO* grad;
     const LogdensIO* dens;
+    const JacIO* jac;         // the Jacobian call: the forward, then k_jac_gpr / k_jac_svgp on the weights
 };
 // The posterior entries' argument checks, in gpr_check_dims' order: handle, d (MFGP_ERR_DIM), the family's
 // sizes, then rest_ok; an SVGP cache without a mixing matrix has a latent per output.

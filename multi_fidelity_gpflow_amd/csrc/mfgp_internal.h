@@ -593,4 +593,52 @@ struct LogpdfArgs {
 void launch_mvn_logpdf(const LogpdfArgs& a, hipStream_t s);
 bool mvn_logpdf_geometry_ok(int ns, int p, bool dense, int ldc, long y_rs, long ov_rs);
 
+// Emulator Jacobian from the cached posterior (mfgp_jacobian.hip), linear multi-fidelity kernel only:
+//   J[s][k][c] = d mean[s][c] / d Xs[s][k] = sum_i alpha[i][c] dK(x_i, xs_s) / d xs[s][k],
+//   dK / d xs[s][k] = (wL / lL_k^2 + wD / lD_k^2)(x_ik - xs_sk), wL = cL vL kL, wD = cD vD kD.
+// k_jac_weights  alpha = L^{-T} Z (GPR, [T NB x Tp NB]) or Lm^{-T} q_mu per latent (SVGP, [batch][T NB]):
+//                one workgroup per output tile, U_j = sum_{i >= j} (L^{-1})_ij^T Z_i on the matrix core.
+// k_jac_gpr      per (column tile of Xs, output tile, chunk of row tiles, group of JacCfg::DG dimensions): the
+//                wL / wD tiles generated in LDS, G_k formed as the MFMA's A operand, acc_k += G_k^T alpha_tile;
+//                chunk partials in `part`, summed in chunk order by the last workgroup to arrive at `cnt`.
+// k_jac_svgp     per (latent, column tile, chunk): dg_l[s][k] partials, the VJP epilogue's contraction with
+//                U = alpha_l (x) 1; k_jac_svgp_sum adds the chunks in order, k_jac_svgp_mix the latents.
+struct JacArgs {
+    const double* Li; long ldl; long sL;      // L^{-1}, lower tiles, batch stride
+    const double* Zc; long ldz;               // GPR: Z tiles; nullptr: SVGP
+    const double* qmu;                        // SVGP: [batch][T NB] cached q_mu columns
+    int T, Tp;
+    double* alpha; long lda; long sA;         // the weights (see k_jac_weights); sA: batch stride
+    const double* X1; long ldx1; int n1;      // cached inputs / inducing points
+    const double* theta; long stheta;
+    const double* Xs; long ldxs; int nstar;
+    int D, p;
+    int Ts, chunk, nch, dgroups;              // column tiles, row tiles per chunk, chunks, dimension groups
+    double* part; int* cnt;                   // GPR: [Ts][Tp][dgroups][nch][dw][NB][NB] (dw = min(DG, D)), [Ts][Tp][dgroups]
+                                              // SVGP: part [batch][nch][Ts][D][NB]
+    double* dgl;                              // SVGP: [batch][Ts][D][NB] (part itself when nch == 1)
+    const double* W; int L;                   // SVGP mixing [p][L]; nullptr: a latent per output
+    double* J; long ldj;                      // [nstar][D][ldj], outputs fastest
+};
+template <int NB> struct JacCfg { static constexpr int DG = NB == 32 ? 16 : 4; };   // accumulators a thread carries
+template <int NB> void launch_jac_weights(const JacArgs& a, int batch, hipStream_t s);
+template <int NB> void launch_jac_gpr(const JacArgs& a, hipStream_t s);
+template <int NB> void launch_jac_svgp(const JacArgs& a, int batch, hipStream_t s);
+
+// mfgp_mvn_fisher (mfgp_density.hip): F_s = J_s^T (obs_cov + diag(var_s + obs_var_s))^{-1} J_s per row s.
+constexpr size_t FISHER_LDS_BYTES = 160 * 1024;     // the dense form's image must fit one CU's LDS
+constexpr size_t MVN_FISHER_WS_BYTES = 256;         // reserved: the kernels keep everything on chip
+struct FisherArgs {
+    int ns, p, d;
+    const double* J; long ldj;                // [ns][d][ldj]
+    const double* var; long var_rs, var_cs;
+    const double* obs_var; long ov_rs;        // nullptr: none
+    const double* obs_cov; long ldc;          // nullptr: the diagonal form
+    double* F;                                // [ns][d][d]
+    int* info;
+};
+size_t fisher_dense_smem(int p, int d);
+bool mvn_fisher_geometry_ok(int ns, int p, int d, bool dense, int ldc, long ov_rs);
+void launch_mvn_fisher(const FisherArgs& a, hipStream_t s);
+
 }  // namespace mfgp

@@ -1,6 +1,7 @@
 // C-ABI entry points of the cached posterior (include/mfgp.h, mfgp_gpr_posterior_size through
-// mfgp_svgp_posterior_logdens): the cache and workspace layouts, the argument blocks and the launch
-// sequences of mfgp_posterior.hip / mfgp_leave_out.hip / mfgp_design.hip / mfgp_append.hip.  Host-side
+// mfgp_svgp_posterior_logdens, and the mfgp_*_jacobian entries): the cache and workspace layouts, the argument
+// blocks and the launch sequences of mfgp_posterior.hip / mfgp_leave_out.hip / mfgp_design.hip / mfgp_append.hip /
+// mfgp_jacobian.hip.  Host-side
 // orchestration only, as the other *_capi.hip files: no allocation, no synchronisation.
 #include <algorithm>
 
@@ -114,8 +115,21 @@ struct PostChain {
     double *gpart, *glat, *Am, *Bm;   // VJP (Am / Bm: SVGP)
     int* gcnt;
     double *gm, *gv;                  // density
-    size_t predict, vjp, logdens;     // bytes of a call of that kind
+    // Jacobian, behind the predict layout (in the VJP part's place): row tiles per chunk, chunks, dimension groups,
+    // the chunk partials, the task counters (GPR) and the latents' sums (SVGP; the partials themselves with one chunk)
+    int jchunk, jnch, jdgroups;
+    double *jpart, *jdgl;
+    int* jcnt;
+    size_t jcnt_bytes;
+    size_t predict, vjp, logdens, jac;   // bytes of a call of that kind
 };
+// The Jacobian's chunk count from the shapes alone: enough tasks for the device's 256 CUs, never more chunks
+// than row tiles.
+static int jac_chunks(int T, long tasks) {
+    const long want = (256 + tasks - 1) / tasks;
+    const int nch = (int)std::max<long>(1, std::min<long>(want, T));
+    return ceil_div(T, ceil_div(T, nch));
+}
 static PostChain post_chain(int nb, const PostDims& s, int nstar, void* ws) {
     PostChain W{};
     const PostLayout& P = W.P = post_layout(nb, s.T, s.Tp, nstar, s.batch, s.svgp, ws);
@@ -130,13 +144,34 @@ static PostChain post_chain(int nb, const PostDims& s, int nstar, void* ws) {
     Behind q(ws, g.end());
     W.gm = q.take<double>((size_t)nstar * s.p);
     W.gv = q.take<double>((size_t)nstar * (s.svgp ? s.p : 1));
-    W.predict = P.bytes; W.vjp = g.end(); W.logdens = q.end();
+    Behind j(ws, P.bytes);
+    const size_t d1 = (size_t)(s.d > 0 ? s.d : 1);
+    if (s.svgp) {
+        W.jdgroups = 1;
+        W.jnch = jac_chunks(s.T, (long)s.batch * P.Ts);
+        W.jpart = j.take<double>((size_t)s.batch * W.jnch * P.Ts * d1 * nb);
+        W.jdgl = W.jnch > 1 ? j.take<double>((size_t)s.batch * P.Ts * d1 * nb) : W.jpart;
+    } else {
+        const int dg = nb == 64 ? JacCfg<64>::DG : JacCfg<32>::DG;
+        const size_t tp = (size_t)(s.Tp > 0 ? s.Tp : 1);
+        W.jdgroups = ceil_div((int)d1, dg);
+        W.jnch = jac_chunks(s.T, (long)(P.Ts * tp) * W.jdgroups);
+        W.jcnt_bytes = (sizeof(int) * P.Ts * tp * W.jdgroups + 15) & ~(size_t)15;
+        W.jcnt = j.take<int>(W.jcnt_bytes / sizeof(int));
+        if (W.jnch > 1)
+            W.jpart = j.take<double>(P.Ts * tp * W.jdgroups * W.jnch * std::min<size_t>(d1, dg) * nb * nb);
+    }
+    W.jchunk = ceil_div(s.T, W.jnch);
+    W.predict = P.bytes; W.vjp = g.end(); W.logdens = q.end(); W.jac = j.end();
     return W;
 }
+// The Jacobian weights buffer: GPR alpha = L^{-T} Z [npad x ppad]; SVGP alpha_l = Lm^{-T} q_mu [l][mpad]
+static size_t jac_weights_bytes(size_t rows, size_t cols) { return Behind::up(sizeof(double) * rows * cols); }
 // What a query asks of a forward driver.  An entry sets at most one of cov, grad and dens: whether the call
 // runs k_post_grad, and the bytes of the chain it needs (a value-only log-density ends behind the density launch).
 static bool post_wants_grad(const PostQuery& q) { return q.grad || (q.dens && q.dens->gX); }
 static size_t post_ws_need(const PostChain& W, const PostQuery& q) {
+    if (q.jac) return W.jac;
     if (q.dens) return q.dens->gX ? W.logdens : W.predict;
     return q.grad ? W.vjp : W.predict;
 }
@@ -165,6 +200,32 @@ static PostArgs gpr_post_args(const GprCache& c, const PostLayout& P, const Post
     a.mpart = P.mpart; a.vpart = P.vpart;
     a.mean = q.mean; a.ldm = q.ldm; a.var = q.var;
     return a;
+}
+
+// The Jacobian kernels' argument block from a GPR cache and its weights buffer; jac_query_args adds the query
+static JacArgs gpr_jac_args(const GprCache& c, double* weights) {
+    JacArgs j{};
+    j.Li = c.LZ; j.ldl = c.ldr;
+    j.Zc = c.LZ + c.npad; j.ldz = c.ldr;
+    j.T = c.T; j.Tp = c.Tp;
+    j.alpha = weights; j.lda = c.ppad;
+    j.X1 = c.X; j.ldx1 = c.d + 1; j.n1 = c.n;
+    j.theta = c.theta;
+    j.D = c.d; j.p = c.p;
+    return j;
+}
+static void jac_query_args(JacArgs& j, const PostChain& W, const PostQuery& q) {
+    j.Xs = q.Xs; j.ldxs = q.ldxs; j.nstar = q.nstar;
+    j.Ts = W.P.Ts; j.chunk = W.jchunk; j.nch = W.jnch; j.dgroups = W.jdgroups;
+    j.part = W.jpart; j.cnt = W.jcnt; j.dgl = W.jdgl;
+    j.J = q.jac->J; j.ldj = q.jac->ldj;
+}
+template <int NB>
+static int gpr_jacobian_weights_impl(mfgp_handle_t h, const GprCacheRef& r, void* weights, size_t weights_bytes) {
+    const GprCache c = gpr_cache_layout(NB, r);
+    if (r.cache_bytes < c.bytes || weights_bytes < jac_weights_bytes(c.npad, c.ppad)) return MFGP_ERR_WORKSPACE;
+    launch_jac_weights<NB>(gpr_jac_args(c, (double*)weights), 1, h->stream);
+    return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
 }
 
 static int gpr_posterior_build_impl(mfgp_handle_t h, const GprProblem& P, const GprCacheRef& r) {
@@ -209,6 +270,7 @@ static int gpr_posterior_forward(mfgp_handle_t h, const GprCacheRef& r, const Po
     const GprCache c = gpr_cache_layout(NB, r);
     const PostChain W = post_chain(NB, post_dims(c), q.nstar, q.ws);
     if (r.cache_bytes < c.bytes || q.ws_bytes < post_ws_need(W, q)) return MFGP_ERR_WORKSPACE;
+    if (q.jac && q.jac->weights_bytes < jac_weights_bytes(c.npad, c.ppad)) return MFGP_ERR_WORKSPACE;
     hipStream_t s = h->stream;
     const bool grad = post_wants_grad(q);
     PostArgs a = gpr_post_args(c, W.P, q, q.cov || grad);
@@ -216,6 +278,12 @@ static int gpr_posterior_forward(mfgp_handle_t h, const GprCacheRef& r, const Po
     launch_post<NB>(a, 1, s);
     if (q.dens) logdens_launch(s, W, q, c.p, false);
     if (grad) launch_post_grad<NB>(a, 1, s);
+    if (q.jac) {
+        (void)hipMemsetAsync(W.jcnt, 0, W.jcnt_bytes, s);
+        JacArgs j = gpr_jac_args(c, (double*)q.jac->weights);
+        jac_query_args(j, W, q);
+        launch_jac_gpr<NB>(j, s);
+    }
     if (q.cov)
         cov_from_a<NB>(s, q.Xs, q.ldxs, q.nstar, c.theta, c.d, c.nlf, W.P.Am, W.P.nspad, c.T, W.P.Kss, W.P.Cov, q.cov,
                        q.ldc);
@@ -436,11 +504,25 @@ static int svgp_posterior_build_impl(mfgp_handle_t h, const SvgpProblem& P, cons
     return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
 }
 
+static JacArgs svgp_jac_args(const SvgpCache& c, const SvgpCacheRef& r, double* weights) {
+    JacArgs j{};
+    j.Li = c.Li; j.ldl = c.mpad; j.sL = (long)c.mpad * c.mpad;
+    j.qmu = c.qmu;
+    j.T = c.Tm; j.Tp = 0;
+    j.alpha = weights; j.sA = c.mpad;
+    j.X1 = c.Z; j.ldx1 = r.d + 1; j.n1 = r.m;
+    j.theta = c.thetas; j.stheta = c.G;
+    j.D = r.d; j.p = r.p;
+    j.W = r.mixed ? c.W : nullptr; j.L = r.l;
+    return j;
+}
+
 // The SVGP forward calls: predict, predict-VJP (q.grad) and log-density (q.dens), as the GPR ones
 static int svgp_posterior_forward(mfgp_handle_t h, const SvgpCacheRef& r, const PostQuery& q) {
     const SvgpCache c = svgp_cache_layout(h->nb, r);
     const PostChain W = post_chain(h->nb, post_dims(h->nb, r), q.nstar, q.ws);
     if (r.cache_bytes < c.bytes || q.ws_bytes < post_ws_need(W, q)) return MFGP_ERR_WORKSPACE;
+    if (q.jac && q.jac->weights_bytes < jac_weights_bytes(r.l, c.mpad)) return MFGP_ERR_WORKSPACE;
     const PostLayout& P = W.P;
     const bool grad = post_wants_grad(q);
     const long mm = (long)c.mpad * c.mpad;
@@ -464,6 +546,18 @@ static int svgp_posterior_forward(mfgp_handle_t h, const SvgpCacheRef& r, const 
     TILE_CALL(h->nb, launch_post, a, r.l, h->stream);
     if (q.dens) logdens_launch(h->stream, W, q, r.p, true);
     if (grad) TILE_CALL(h->nb, launch_post_grad, a, r.l, h->stream);
+    if (q.jac) {
+        JacArgs j = svgp_jac_args(c, r, (double*)q.jac->weights);
+        jac_query_args(j, W, q);
+        TILE_CALL(h->nb, launch_jac_svgp, j, r.l, h->stream);
+    }
+    return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
+}
+static int svgp_jacobian_weights_impl(mfgp_handle_t h, const SvgpCacheRef& r, void* weights, size_t weights_bytes) {
+    const SvgpCache c = svgp_cache_layout(h->nb, r);
+    if (r.cache_bytes < c.bytes || weights_bytes < jac_weights_bytes(r.l, c.mpad)) return MFGP_ERR_WORKSPACE;
+    const JacArgs j = svgp_jac_args(c, r, (double*)weights);
+    TILE_CALL(h->nb, launch_jac_weights, j, r.l, h->stream);
     return last() == hipSuccess ? MFGP_OK : MFGP_ERR_LAUNCH;
 }
 
@@ -743,6 +837,84 @@ int mfgp_svgp_posterior_logdens(mfgp_handle_t h, int nstar, int m, int l, int p,
     const PostQuery q{nstar, Xs, ldxs, ws, ws_bytes, f_mu, p, f_var, nullptr, 0, nullptr, &dn};
     const bool ok = nstar > 0 && post_query_ok(q, cache, p, d) && logdens_io_ok(dn, nstar, p, d);
     if (const int rc = svgp_post_check(h, c, ok)) return rc;
+    return svgp_posterior_forward(h, c, q);
+}
+
+// ---- the Jacobian entries (mfgp_jacobian.hip).  The linear multi-fidelity kernel only: nlf > 0 is MFGP_ERR_ARG
+// behind the handle and d, as the VJP entries; the nstar == 0 return next, everything else behind it.
+
+int mfgp_gpr_jacobian_weights_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, size_t* bytes) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nlf != 0) return MFGP_ERR_ARG;
+    const GprCacheRef c{nlf, n, p, d};
+    if (const int rc = gpr_post_check(h, c, bytes != nullptr)) return rc;
+    const GprCache g = gpr_cache_layout(h->nb, c);
+    *bytes = jac_weights_bytes(g.npad, g.ppad);
+    return MFGP_OK;
+}
+
+int mfgp_gpr_jacobian_weights(mfgp_handle_t h, int nlf, int n, int p, int d, const void* cache, size_t cache_bytes,
+                              void* weights, size_t weights_bytes) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nlf != 0) return MFGP_ERR_ARG;
+    const GprCacheRef c{nlf, n, p, d, cache, cache_bytes};
+    if (const int rc = gpr_post_check(h, c, cache && weights)) return rc;
+    return TILE_CALL(h->nb, gpr_jacobian_weights_impl, h, c, weights, weights_bytes);
+}
+
+int mfgp_gpr_jacobian_workspace_size(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar, size_t* bytes) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nlf != 0) return MFGP_ERR_ARG;
+    return gpr_post_ws_size(h, GprCacheRef{nlf, n, p, d}, nstar, &PostChain::jac, bytes);
+}
+
+int mfgp_gpr_jacobian(mfgp_handle_t h, int nlf, int n, int p, int d, int nstar, const void* cache, size_t cache_bytes,
+                      const void* weights, size_t weights_bytes, const double* Xs, int ldxs, void* ws, size_t ws_bytes,
+                      double* mean, int ldm, double* var, double* J, int ldj) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nlf != 0) return MFGP_ERR_ARG;   // the graph kernel's per-source derivative is not built
+    if (nstar == 0) return MFGP_OK;
+    const GprCacheRef c{nlf, n, p, d, cache, cache_bytes};
+    const JacIO jio{weights, weights_bytes, J, ldj};
+    const PostQuery q{nstar, Xs, ldxs, ws, ws_bytes, mean, ldm, var, nullptr, 0, nullptr, nullptr, &jio};
+    if (const int rc = gpr_post_check(h, c, nstar > 0 && post_query_ok(q, cache, p, d) && weights && J && ldj >= p))
+        return rc;
+    return TILE_CALL(h->nb, gpr_posterior_forward, h, c, q);
+}
+
+int mfgp_svgp_jacobian_weights_workspace_size(mfgp_handle_t h, int m, int l, int p, int d, size_t* bytes) {
+    const SvgpCacheRef c{m, l, p, d, 1};
+    if (const int rc = svgp_post_check(h, c, bytes != nullptr)) return rc;
+    *bytes = jac_weights_bytes(l, svgp_cache_layout(h->nb, c).mpad);
+    return MFGP_OK;
+}
+
+int mfgp_svgp_jacobian_weights(mfgp_handle_t h, int m, int l, int p, int d, int mixed, const void* cache,
+                               size_t cache_bytes, void* weights, size_t weights_bytes) {
+    const SvgpCacheRef c{m, l, p, d, mixed, cache, cache_bytes};
+    if (const int rc = svgp_post_check(h, c, cache && weights)) return rc;
+    return svgp_jacobian_weights_impl(h, c, weights, weights_bytes);
+}
+
+int mfgp_svgp_jacobian_workspace_size(mfgp_handle_t h, int nstar, int m, int l, int p, int d, size_t* bytes) {
+    return svgp_post_ws_size(h, SvgpCacheRef{m, l, p, d, 1}, nstar, &PostChain::jac, bytes);
+}
+
+int mfgp_svgp_jacobian(mfgp_handle_t h, int nstar, int m, int l, int p, int d, int mixed, const void* cache,
+                       size_t cache_bytes, const void* weights, size_t weights_bytes, const double* Xs, int ldxs,
+                       void* ws, size_t ws_bytes, double* f_mu, double* f_var, double* J, int ldj) {
+    CHECK_H(h);
+    CHECK_D(d);
+    if (nstar == 0) return MFGP_OK;
+    const SvgpCacheRef c{m, l, p, d, mixed, cache, cache_bytes};
+    const JacIO jio{weights, weights_bytes, J, ldj};
+    const PostQuery q{nstar, Xs, ldxs, ws, ws_bytes, f_mu, p, f_var, nullptr, 0, nullptr, nullptr, &jio};
+    if (const int rc = svgp_post_check(h, c, nstar > 0 && post_query_ok(q, cache, p, d) && weights && J && ldj >= p))
+        return rc;
     return svgp_posterior_forward(h, c, q);
 }
 

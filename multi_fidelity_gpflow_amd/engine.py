@@ -800,6 +800,81 @@ class Engine:
         return self._posterior_logdens("svgp", (Xs.shape[0], m, L, p, d), (1 if mixed else 0,), p, d, cache, Xs, Y,
                                        obs_var, obs_cov, grad)
 
+    # ---- emulator Jacobian and Fisher matrix (include/mfgp.h mfgp_*_jacobian, mfgp_mvn_fisher)
+    def _jacobian_weights(self, fam, dims, flags, cache):
+        """alpha of `cache` in a new device buffer (mfgp_*_jacobian_weights: one launch, once per cache block)."""
+        nbytes = self._size(getattr(self.lib, f"mfgp_{fam}_jacobian_weights_workspace_size"), *dims)
+        w = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        name = f"mfgp_{fam}_jacobian_weights"
+        check(getattr(self.lib, name)(self.h, *dims, *flags, ptr(cache), cache.numel(), ptr(w), w.numel()), name)
+        return w
+
+    def _jacobian(self, fam, dims, flags, p, d, cache, weights, Xs):
+        gpr = fam == "gpr"
+        ns = Xs.shape[0]
+        f64 = dict(dtype=torch.float64, device=self.device)
+        mean, var = torch.empty((ns, p), **f64), torch.empty((ns,) if gpr else (ns, p), **f64)
+        J = torch.empty((ns, d, p), **f64)
+        if ns:
+            head = (*dims, *flags, ptr(cache), cache.numel(), ptr(weights), weights.numel(), ptr(Xs), Xs.shape[1])
+            outs = (ptr(mean), p, ptr(var)) if gpr else (ptr(mean), ptr(var))
+            self._posterior_run(f"mfgp_{fam}_jacobian", "post_jac", dims, head, (*outs, ptr(J), p))
+        return mean, var, J
+
+    def gpr_jacobian_weights(self, shape, cache):
+        n, p, d = shape
+        return self._jacobian_weights("gpr", (0, n, p, d), (), cache)
+
+    def gpr_jacobian(self, shape, cache, weights, Xs):
+        """mfgp_gpr_jacobian: the predict forward and the Jacobian kernel -> (mean [ns, p], var [ns],
+        J [ns, d, p], the device layout: outputs fastest).  No host read of a device word."""
+        n, p, d = shape
+        return self._jacobian("gpr", (0, n, p, d, Xs.shape[0]), (), p, d, cache, weights, Xs)
+
+    def svgp_jacobian_weights(self, shape, cache):
+        m, L, p, d, mixed = shape
+        return self._jacobian_weights("svgp", (m, L, p, d), (1 if mixed else 0,), cache)
+
+    def svgp_jacobian(self, shape, cache, weights, Xs):
+        """mfgp_svgp_jacobian -> (f_mu [ns, p], f_var [ns, p], J [ns, d, p])."""
+        m, L, p, d, mixed = shape
+        return self._jacobian("svgp", (Xs.shape[0], m, L, p, d), (1 if mixed else 0,), p, d, cache, weights, Xs)
+
+    def mvn_fisher(self, J, var, obs_var=None, obs_cov=None):
+        """Batched Fisher matrix (include/mfgp.h mfgp_mvn_fisher): J [ns, d, p] (the Jacobian's device layout),
+        var [ns] (one variance per row, GPR) or [ns, p], obs_var None / [p] / [ns, p], obs_cov None / [p, p] ->
+        (F [ns, d, d], info [ns] int32).  No host read of a device word."""
+        ns, d, p = J.shape
+        if var.dim() == 1 and var.shape[0] == ns:
+            var_rs, var_cs = 1, 0
+        elif tuple(var.shape) == (ns, p):
+            var_rs, var_cs = p, 1
+        else:
+            raise ValueError(f"mvn_fisher: var has shape {tuple(var.shape)}, expected ({ns},) or ({ns}, {p})")
+        ov, ov_rs = None, 0
+        if obs_var is not None:
+            if tuple(obs_var.shape) not in ((p,), (ns, p)):
+                raise ValueError(f"mvn_fisher: obs_var has shape {tuple(obs_var.shape)}, expected ({p},) or ({ns}, {p})")
+            ov, ov_rs = obs_var.contiguous(), (p if obs_var.dim() == 2 else 0)
+        ldc = 0
+        if obs_cov is not None:
+            if tuple(obs_cov.shape) != (p, p):
+                raise ValueError(f"mvn_fisher: obs_cov has shape {tuple(obs_cov.shape)}, expected ({p}, {p})")
+            r = ((p + 7) & ~7) + d
+            if p > 128 or r * (r | 1) * 8 > 160 * 1024:
+                raise ValueError(f"mvn_fisher: the dense form (obs_cov) is built for P <= 128 outputs and P8 + D <= 143, "
+                                 f"got P = {p}, D = {d}; use the diagonal form")
+            if (p > 1 and obs_cov.stride(1) != 1) or obs_cov.stride(0) < p:
+                obs_cov = obs_cov.contiguous()
+            ldc = max(obs_cov.stride(0), p)
+        J, var = J.contiguous(), var.contiguous()
+        F = torch.empty((ns, d, d), dtype=torch.float64, device=self.device)
+        info = torch.zeros((ns,), dtype=torch.int32, device=self.device)
+        ws = self.workspace("mvn_fisher", self._size(self.lib.mfgp_mvn_fisher_workspace_size, ns, p, d))
+        check(self.lib.mfgp_mvn_fisher(self.h, ns, p, d, ptr(J), p, ptr(var), var_rs, var_cs, ptr(ov), ov_rs,
+                                       ptr(obs_cov), ldc, ptr(ws), ws.numel(), ptr(F), ptr(info)), "mfgp_mvn_fisher")
+        return F, info
+
     def selftest_mfma(self) -> np.ndarray:
         out = torch.zeros((16, 16), dtype=torch.float64, device=self.device)
         check(self.lib.mfgp_selftest_mfma(self.h, ptr(out)), "mfgp_selftest_mfma")

@@ -36,6 +36,13 @@ Inference: ``log_density(Xnew, Y, obs_cov, obs_var, grad)`` is the emulator log-
 one call (``mfgp_*_posterior_logdens``: the forward once, a batched [P, P] density kernel in LDS
 (``mfgp_mvn_logpdf``), then the VJP kernel fed the density's own gradients).  ``predict_log_density`` is GPflow's
 method of that name on the marginal prediction, for the four models and both posterior classes.
+
+First-order objects: ``mean_jacobian(Xnew)`` is the Jacobian of the emulated data vector w.r.t. the input
+parameters, [N*, P, D], from one call (``mfgp_*_jacobian``: the forward once, then one product against
+``alpha = K^{-1} Y`` with dK/dx generated on chip), and ``fisher(Xnew, obs_cov, obs_var)`` the Fisher
+(Gauss-Newton) matrix ``J^T Sigma^{-1} J`` per row built from it (``mfgp_mvn_fisher``: the [P, P] factorization in
+LDS carries the rows of J^T along, so F falls out of it): what forecasts, Laplace approximations and HMC
+preconditioning are built from.
 """
 from __future__ import annotations
 
@@ -289,6 +296,35 @@ def predict_log_density_of(model, predict_f, data, full_cov=False, full_output_c
     return as_result(logp)
 
 
+FISHER_LDS_BYTES = 160 * 1024   # the dense Fisher form's LDS image must fit one compute unit (include/mfgp.h mfgp_mvn_fisher)
+
+
+class FisherResult(NamedTuple):
+    """What ``fisher`` returns (device tensors, detached)."""
+    fisher: torch.Tensor      # [N*, D, D] J_s^T (diag(var_s + obs_var_s) + obs_cov)^{-1} J_s, exactly symmetric
+    mean: torch.Tensor        # [N*, P] predict_f's mean (the same bits)
+    var: torch.Tensor         # [N*, P] predict_f's marginal variance (the same bits)
+    jacobian: torch.Tensor    # [N*, P, D] d mean / d Xnew, what mean_jacobian returns
+
+
+def fisher_dense_fits(p: int, d: int) -> bool:
+    """Whether the dense Fisher form is built for P = p outputs and D = d inputs: P <= 128 and the LDS image of
+    (P8 + D) x ((P8 + D) | 1) doubles, P8 = P rounded up to 8, within the 160 KiB of a compute unit
+    (P8 + D <= 143: D <= 15 at P = 128, any D <= 32 up to P = 104)."""
+    r = ((int(p) + 7) & ~7) + int(d)
+    return p <= MAX_DENSE_OUTPUTS and r * (r | 1) * 8 <= FISHER_LDS_BYTES
+
+
+def fisher_plan(what, ns, p, d, obs_var, obs_cov):
+    """The argument checks of fisher's obs_var / obs_cov, on the host before any device work: density_plan's
+    (the same forms as log_density), then the dense form's limit."""
+    density_plan(what, ns, p, np.empty((p,)), obs_var, obs_cov)
+    if obs_cov is not None and not fisher_dense_fits(p, d):
+        raise ValueError(f"{what}: the dense form (obs_cov) is built for P <= {MAX_DENSE_OUTPUTS} outputs and "
+                         f"P8 + D <= 143 (P8 = P rounded up to 8; the [P8 + D]^2 image must fit the 160 KiB of LDS), "
+                         f"got P = {p}, D = {d}; pass a diagonal obs_var instead")
+
+
 MAX_GROUP = 32   # rows of one left-out group (include/mfgp.h mfgp_gpr_posterior_leave_out: gmax <= 32)
 
 
@@ -477,6 +513,7 @@ class _Posterior:
         update succeeds, a TENSOR one keeps its previous contents."""
         if precompute_cache is not None:
             self._precompute_cache = _cache_type(precompute_cache)
+        self._jac_weights = None   # they belong to the block's contents: a VARIABLE cache is rewritten in place
         if self._precompute_cache is PrecomputeCacheType.NOCACHE:
             self.cache, self._valid = None, False
             return
@@ -499,6 +536,7 @@ class _Posterior:
                 raise CholeskyError(f"{what}: Cholesky of K_uu was not successful")
             raise info_error(bad, what)
         self.cache, self._valid = buf, True
+        self._jac_weights = None
 
     def predict_f_vjp(self, Xnew, grad_mean, grad_var=None):
         """The marginal predict_f at the snapshot and its vector-Jacobian product w.r.t. Xnew:
@@ -578,6 +616,68 @@ class _Posterior:
         raise_density_info(what, info, oc is not None)
         return LogDensityResult(as_result(logp), as_result(mean), as_result(var),
                                 None if gX is None else as_result(gX))
+
+    def mean_jacobian(self, Xnew):
+        """The marginal predict_f at the snapshot and the Jacobian of its mean w.r.t. Xnew, from one call:
+        ``(mean [N*, P], var [N*, P], jac [N*, P, D])`` with ``jac[s, c, k] = d mean[s, c] / d Xnew[s, k]`` over
+        the D input columns only (the fidelity column enters through exact ``== 0`` / ``== 1`` tests, has no
+        derivative and no slot).  mfgp_*_jacobian: the predict call's own forward (mean / var carry predict_f's
+        bits; it runs once) and one product against ``alpha = K^{-1} Y`` (SVGP: ``Lm^{-T} q_mu`` per latent)
+        with dK/dx generated on chip -- not P one-hot ``predict_f_vjp`` calls.  ``jac`` is a transposed VIEW
+        of the device layout [N*, D, P] (outputs fastest, what the kernel writes coalesced and ``fisher``
+        reads): call ``.contiguous()`` for a dense [N*, P, D].  ``alpha`` is computed on first use and kept
+        beside the cache block until ``update_cache()``.  Detached, deterministic (the same inputs give the
+        same bits); no host read of a device word.  ValueError for a wrong Xnew shape, NotImplementedError for
+        a NOCACHE posterior and for the graph model (as predict_f_vjp), all before any device work.  N* = 0
+        returns empty tensors without a launch."""
+        what = "mean_jacobian"
+        self._need_cache(f"{what}: a NOCACHE posterior has no cached factors; use a TENSOR or VARIABLE cache")
+        self._check_vjp()
+        _design_rows(Xnew, self._input_dim(), f"{what}: Xnew")
+        eng = self._engine()   # every ValueError of the arguments is raised above
+        mean, var, J = self._jacobian(eng, to_dev(Xnew, eng.device))
+        return as_result(mean), as_result(var), as_result(J.transpose(1, 2))
+
+    def fisher(self, Xnew, obs_cov=None, obs_var=None) -> FisherResult:
+        """The Fisher (Gauss-Newton) matrix of the emulated data vector at every row of Xnew:
+        ``F[s] = J_s^T (diag(var(Xnew_s) + obs_var_s) + obs_cov)^{-1} J_s`` [N*, D, D], with ``J_s`` the
+        ``mean_jacobian`` and the covariance exactly the one ``log_density`` uses: ``obs_var`` a scalar, [P] or
+        [N*, P], ``obs_cov`` [P, P] symmetric positive definite (its lower triangle is read); both may be given
+        and are added; the emulator's own likelihood noise is NOT added.  One Jacobian call and one launch of
+        mfgp_mvn_fisher: with ``obs_cov`` the [P, P] covariance of every row is factored in LDS with the rows
+        of J^T carried along, so F falls out of the factorization (no [N*, P, P] tensor, no rocSOLVER call);
+        without it the diagonal form runs (any P).  F is exactly symmetric (one triangle is computed and
+        mirrored).  This is the MEAN term of the Gaussian Fisher information; the
+        ``1/2 tr(Sigma^-1 dSigma Sigma^-1 dSigma)`` term that dvar/dx adds is not formed.
+
+        Returns ``FisherResult(fisher, mean, var, jacobian)``, detached.  ValueError before any device work
+        for a wrong shape, a negative obs_var, or an obs_cov beyond the dense form's limit (P <= 128 and
+        P8 + D <= 143, ``fisher_dense_fits``); NotImplementedError for a NOCACHE posterior and the graph model.
+        The call's one host read is info, after everything is enqueued: CholeskyError naming the row whose
+        covariance is not positive definite (e.g. a NaN input row)."""
+        what = "fisher"
+        self._need_cache(f"{what}: a NOCACHE posterior has no cached factors; use a TENSOR or VARIABLE cache")
+        self._check_vjp()
+        p, d = self._num_outputs(), self._input_dim()
+        ns = _design_rows(Xnew, d, f"{what}: Xnew")
+        fisher_plan(what, ns, p, d, obs_var, obs_cov)
+        eng = self._engine()   # every ValueError of the arguments is raised above
+        _, ov, oc = density_inputs(eng, p, np.zeros((p,)), obs_var, obs_cov)
+        mean, var, J = self._jacobian(eng, to_dev(Xnew, eng.device), tiled=False)
+        F, info = eng.mvn_fisher(J, var, ov, oc)
+        if var.dim() == 1:
+            var = var[:, None].expand(-1, p).contiguous()
+        raise_density_info(what, info, oc is not None)
+        return FisherResult(as_result(F), as_result(mean), as_result(var), as_result(J.transpose(1, 2)))
+
+    def _weights(self, eng: Engine):
+        """alpha of the current cache block (Engine.*_jacobian_weights), built on first use; update_cache() and
+        _commit() drop it.  (Posteriors are also made with object.__new__: read with a default.)"""
+        w = getattr(self, "_jac_weights", None)
+        if w is None or w[0] is not self.cache:
+            w = (self.cache, self._make_weights(eng))
+            self._jac_weights = w
+        return w[1]
 
     def predict_log_density(self, data, full_cov: bool = False, full_output_cov: bool = False):
         """GPflow ``GPModel.predict_log_density((Xnew, Ynew))`` on this posterior's marginal predict_f:
@@ -765,6 +865,15 @@ class GPRPosterior(_Posterior):
                                                               obs_cov, grad)
         return mean, var[:, None].expand(-1, self._shape[1]).contiguous(), logp, gX, info
 
+    def _make_weights(self, eng):
+        return eng.gpr_jacobian_weights(self._shape, self.cache)
+
+    def _jacobian(self, eng, Xs, tiled=True):
+        """(mean, var [N*, P] -- [N*] with tiled=False --, J [N*, D, P]) on the current cache block."""
+        w = self._weights(eng) if Xs.shape[0] else None   # (an empty call launches nothing)
+        mean, var, J = eng.gpr_jacobian(self._shape, self.cache, w, Xs)
+        return mean, (var[:, None].expand(-1, self._shape[1]).contiguous() if tiled else var), J
+
     def _joint(self, eng, Xs):
         """(mean [N*, P], the ONE [1, N*, N*] block, ncol = P): never tiled over P, factored once."""
         mean, _, cov = eng.gpr_posterior_predict(self._nlf, self._shape, self.cache, Xs, True)
@@ -945,6 +1054,13 @@ class SVGPPosterior(_Posterior):
 
     def _logdens(self, eng, Xs, Y, obs_var, obs_cov, grad):
         return eng.svgp_posterior_logdens(self._shape, self.cache, Xs, Y, obs_var, obs_cov, grad)
+
+    def _make_weights(self, eng):
+        return eng.svgp_jacobian_weights(self._shape, self.cache)
+
+    def _jacobian(self, eng, Xs, tiled=True):
+        w = self._weights(eng) if Xs.shape[0] else None
+        return eng.svgp_jacobian(self._shape, self.cache, w, Xs)
 
     def _joint(self, eng, Xs):
         """(mean [N*, P], cov [P, N*, N*] of the snapshot, ncol = 1): one factor per output."""
